@@ -11,10 +11,18 @@ Multi-GPU: one process per GPU (torchrun); every rank decodes its own file (file
 data-path collective; the only collectives are the timing barrier and the max-over-ranks).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c2r|c2x|c2g|c2l|c1|c1s|c3|c4|c5|wal|idx|enc|readat]
+                    [--full] [--dump-outputs DIR]
 
 c5 (SSTable load + validation + scan), wal (ordered WAL replay from host files) idx (batched
 DiskKeyIndex.Get) and enc (device v4 encode) print their own
 metric lines; the default (c2) line is the BASELINE.json metric.
+
+A run without --full does what its line's headline needs and no more: generate the file, place it in HBM,
+warm up, time exactly --steps steps, check that they rebuilt the warmup's result, print the line. --full adds
+the legs that take runs of their own: the CPU baseline on the oracle with the full-file oracle comparison
+(`verified`), the end-to-end PCIe rates, the two live rocprofv3 --pmc passes behind roofline.traffic, the WAL
+line's worker / depth variants. --dump-outputs DIR writes the arrays the last timed step produced as
+DIR/<name>.npy (inputs are seeded: the same arguments give the same inputs, so two builds compare file by file).
 """
 from __future__ import annotations
 
@@ -161,6 +169,63 @@ def device_digest(t) -> str:
     if n > n8:
         parts += [int(x) for x in u8[n8:].cpu().tolist()]
     return "%x" % (hash(tuple(parts)) & (2**64 - 1))
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # all of a run's --dump-outputs files together (under the 64 MB a dump may take)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(out_dir: str, arrays: dict, writers: int = 1) -> dict:
+    """--dump-outputs: write each named array (a torch tensor on any device, or a numpy array) to
+    out_dir/<name>.npy, float32 where that holds every value exactly (8- and 16-bit integers, float32 and
+    narrower), float64 otherwise (64-bit offsets stay exact below 2^53). Every array gets an equal share of
+    DUMP_BUDGET_BYTES / writers (the ranks or device slots that each write their own arrays); one that does not
+    fit is written as a sample at sorted positions drawn by a generator seeded with DUMP_SEED and the array's
+    length, so two runs with the same arguments sample the same places. Returns {name: [elements written,
+    elements in the array]}."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, writers) // max(1, len(arrays))
+    written = {}
+    for name, a in arrays.items():
+        is_torch = not isinstance(a, np.ndarray)
+        a = a.reshape(-1)
+        n = int(a.shape[0])
+        item = a.element_size() if is_torch else a.dtype.itemsize
+        is_float = a.dtype.is_floating_point if is_torch else a.dtype.kind == "f"
+        wide = np.float32 if item <= 2 or (is_float and item <= 4) else np.float64
+        keep = share // np.dtype(wide).itemsize
+        if n > keep:
+            idx = np.sort(np.random.default_rng([DUMP_SEED, n]).integers(0, n, keep))
+            if is_torch:
+                import torch
+
+                a = a[torch.from_numpy(idx).to(a.device)]
+            else:
+                a = a[idx]
+        host = a.cpu().numpy() if is_torch else a
+        np.save(os.path.join(out_dir, name + ".npy"), host.astype(wide))
+        written[name] = [int(host.shape[0]), n]
+    return written
+
+
+def decode_arrays(files: list, prefix: str = "") -> dict:
+    """The --dump-outputs arrays of a decode step: every file's out, out_off, rec_off and flags (torch
+    tensors, as DeviceBackend.outputs gives them), named <prefix>[file<k>_]<array>. An arena is usually
+    too large to be written whole, so beside its sample goes out_block_sums: the byte sum of each 4096-byte
+    block of it (the last entry: the tail's), which every byte of the arena enters."""
+    import torch
+
+    named = {}
+    for k, (out, out_off, rec_off, flags) in enumerate(files):
+        p = prefix + (f"file{k}_" if len(files) > 1 else "")
+        m = out.numel() // 4096 * 4096
+        sums = torch.cat([out[:m].view(-1, 4096).sum(dim=1, dtype=torch.int64),
+                          out[m:].sum(dtype=torch.int64).reshape(1)])
+        named.update({p + "out": out, p + "out_off": out_off, p + "rec_off": rec_off, p + "flags": flags,
+                      p + "out_block_sums": sums})
+    return named
 
 
 def source_tree_hash(root: str = HERE) -> str:
@@ -513,7 +578,7 @@ def run_sstable(args, world, rank, local, device):
         T["db"], di = decd.decode(T["d_data"], T["ld"], comp=T["cd"])
         if ii["n_records"] != n or di["n_records"] != n:
             raise RuntimeError(f"sstable decode failed: {ii} {di}")
-        T["nb_d"] = di["total_out_bytes"]
+        T["nb_d"], T["nb_i"] = di["total_out_bytes"], ii["total_out_bytes"]
         for k in ("key_off", "key_len", "value_off", "checksum", "crc"):
             T[k] = torch.empty(n, **i64)
         T["pres"], T["vres"] = torch.empty(2, **i64), torch.empty(2, **i64)
@@ -567,6 +632,15 @@ def run_sstable(args, world, rank, local, device):
     dt = time.perf_counter() - t0
     if digests() != want:
         raise RuntimeError("sstable bench: the timed steps did not rebuild the warmup's outputs")
+    if args.dump_outputs:
+        named = {}
+        for t, T in zip(mine, tables):
+            named.update({f"table{t}_index_out": T["ib"].out[:T["nb_i"]], f"table{t}_index_out_off": T["ib"].out_off[:n + 1],
+                          f"table{t}_data_out": T["db"].out[:T["nb_d"]], f"table{t}_data_out_off": T["db"].out_off[:n + 1]})
+            named.update({f"table{t}_{k}": T[k] for k in ("key_off", "key_len", "value_off", "pres", "vres")})
+            for k in ("checksum", "crc"):  # 64-bit CRCs: two 32-bit halves, each exact in float64
+                named[f"table{t}_{k}_hi"], named[f"table{t}_{k}_lo"] = (T[k] >> 32) & 0xFFFFFFFF, T[k] & 0xFFFFFFFF
+        dump_outputs(args.dump_outputs, named, writers=world)
     if world > 1:
         torch.distributed.barrier()
     ev = []
@@ -703,7 +777,7 @@ def run_wal(args, world, rank, local, device):
         dt = timed(W, D, args.steps)
         value, ms_per_step, _ = job_throughput(dt, total_in, args.steps, world, device)
         variants = {}
-        if rank == 0 and world == 1:
+        if rank == 0 and world == 1 and args.full:
             for w, d in ((1, 1), (1, 4), (3, 4), (4, 6)):
                 variants[f"workers{w}_depth{d}"] = round(total_in * 2 / 2**30 / timed(w, d, 2), 3)
         pcie = (total_in + total_out + 9 * WAL_FILES * WAL_RECORDS_PER_FILE) * args.steps / dt / 1e9
@@ -805,6 +879,13 @@ def run_index(args, world, rank, local, device):
     torch.cuda.synchronize(device)
     dt = time.perf_counter() - t0
     kern_ms = ev0.elapsed_time(ev1) / args.steps
+    if args.dump_outputs:
+        w = d_hits.view(torch.int64).view(nq, 4)  # rio_index_hit: offset, value_offset, checksum, {status, found}
+        p = f"rank{rank}_" if world > 1 else ""
+        dump_outputs(args.dump_outputs,
+                     {p + "hit_offset": w[:, 0], p + "hit_value_offset": w[:, 1], p + "hit_checksum_hi": (w[:, 2] >> 32) & 0xFFFFFFFF,
+                      p + "hit_checksum_lo": w[:, 2] & 0xFFFFFFFF, p + "hit_status": w[:, 3] & 0xFFFFFFFF,
+                      p + "hit_found": (w[:, 3] >> 32) & 0xFFFFFFFF}, writers=world)
     value, ms_per_step, _ = job_throughput(dt, nq, args.steps, world, device)
     value *= 2**30  # job_throughput reports units / 2^30 per second; here the unit is one lookup
     alg = nq * (20 + 8 + hit_sz)  # key + its offset in, one hit out
@@ -898,6 +979,10 @@ def run_encode(args, world, rank, local, device):
     torch.cuda.synchronize(device)
     dt = time.perf_counter() - t0
     step_ms = ev0.elapsed_time(ev1) / args.steps
+    if args.dump_outputs:
+        p = f"rank{rank}_" if world > 1 else ""
+        dump_outputs(args.dump_outputs, {p + "file": d_out[:int(d_len.item())], p + "rec_off": d_roff, p + "file_len": d_len},
+                     writers=world)
     value, ms_per_step, _ = job_throughput(dt, total, args.steps, world, device)
     alg = total + 9 * n + flen  # records + offsets/flags in, the file out
     line = {
@@ -1084,6 +1169,16 @@ class DeviceBackend:
         self.sync()
         return res
 
+    def outputs(self):
+        """What the last step handed its caller, per file: (out, out_off, rec_off, flags) cut to the decoded
+        sizes, as torch tensors (--dump-outputs)."""
+        res = []
+        for b in self.bufs:
+            i = self.dec.info(b)
+            n, nb = i["n_records"], i["total_out_bytes"]
+            res.append((b.out[:nb], b.out_off[:n + 1], b.rec_off[:n], b.flags[:n]))
+        return res
+
     def set_timing(self, slots: int):
         from recordio import _lib as L
 
@@ -1180,6 +1275,10 @@ def run_decode(args, world, rank, backend, sizes=None) -> dict:
                                f"{now_infos} / {now_dig} vs {infos} / {digests}")
 
     verify("timed steps")
+    dumped = None
+    if getattr(args, "dump_outputs", None) and lengths:
+        dumped = dump_outputs(args.dump_outputs, decode_arrays(backend.outputs(), f"rank{rank}_" if world > 1 else ""),
+                              writers=world)
 
     value, ms_per_step, dt_max = job_throughput(dt, length, args.steps, world)
 
@@ -1279,6 +1378,8 @@ def run_decode(args, world, rank, backend, sizes=None) -> dict:
         line["mall_flushed"] = mall_flushed
     if warm:
         line["warm_mall"] = warm
+    if dumped:
+        line["dumped_outputs"] = {"dir": args.dump_outputs, "written_of_total": dumped}
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         def against_oracle(out, out_off, rec_off, flags):
             """The oracle's decode of images[0] against the device arrays the timed steps left (their digests)."""
@@ -1384,6 +1485,8 @@ def run_decode_inproc(args, devices: list[int], make_be, sizes=None) -> dict:
             be.set_timing(0)
             if be.infos() != infos[k] or be.checksums() != digests[k]:
                 raise RuntimeError(f"bench: device slot {k}'s timed steps decoded different results from its warmup")
+            if getattr(args, "dump_outputs", None):
+                dump_outputs(args.dump_outputs, decode_arrays(be.outputs(), f"slot{k}_"), writers=nd)
     total = sum(lengths)
     value = total * args.steps / 2**30 / dt
     n = sum(i["n_records"] for inf in infos for i in inf)
@@ -1471,11 +1574,28 @@ def main(argv: list[str] | None = None):
     ap.add_argument("--inproc-devices", default=None,
                     help="in-process multi-device mode: a device list (\"0,1,2,3\", or N for 0..N-1); one process, "
                          "one host thread per device (the Go caller's shape, INTEGRATION.md §2.2)")
-    ap.add_argument("--traffic", default="live", choices=["live", "file", "none"],
+    ap.add_argument("--traffic", default=None, choices=["live", "file", "none"],
                     help="roofline.traffic: measured by this run (two rocprofv3 --pmc passes, 1 GPU only), the "
-                         "committed PMC file, or none")
+                         "committed PMC file, or none (default: live with --full, none without)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the CPU baseline with the oracle comparison "
+                         "(verified), the end-to-end rates, the live PMC traffic passes, the WAL line's variants; "
+                         "--no-cpu-baseline, --no-e2e and --traffic pick among them. Without --full a run sets up, "
+                         "warms up, times --steps steps and prints its line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step computed to DIR/<name>.npy (float32 / "
+                         "float64; a fixed seeded sample of an array too large for its share of 48 MB)")
     argv = sys.argv[1:] if argv is None else argv
     args = ap.parse_args(argv)
+    if not args.full:
+        args.no_cpu_baseline = args.no_e2e = True
+    if args.traffic is None:
+        args.traffic = "live" if args.full else "none"
+    if args.dump_outputs and args.config in ("wal", "readat"):
+        ap.error(f"--dump-outputs: the {args.config} line hands its records over inside the host library and keeps "
+                 "no arrays to write")
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
     rc = launch_contract(args.gpus, argv)
     if rc is not None:
         sys.exit(rc)

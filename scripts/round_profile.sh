@@ -14,7 +14,7 @@ step() {
 }
 step gpu_tests 1100 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench 600 python bench.py
+step bench 600 python bench.py --full
 grep '^{' "$OUT/bench.log" > "$OUT/bench.json" || true
 step rocprof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
     python bench.py --no-cpu-baseline --no-e2e --traffic none

@@ -97,6 +97,13 @@ class OracleBackend:
     def set_timing(self, slots):
         pass
 
+    def outputs(self):
+        import numpy as np
+
+        return [(torch.from_numpy(r["out"]), torch.from_numpy(np.asarray(r["out_off"]).astype(np.int64)),
+                 torch.from_numpy(np.asarray(r["rec_off"]).astype(np.int64)), torch.from_numpy(r["flags"]))
+                for r in self.res]
+
     def checksums(self):
         import hashlib
 
