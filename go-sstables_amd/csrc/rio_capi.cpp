@@ -57,6 +57,10 @@ hipError_t launch_encode(const EncParams& P, void* cub_tmp, size_t cub_bytes, hi
 uint64_t enc_scratch_bytes(uint64_t n, uint64_t bytes, uint32_t compression);
 uint64_t enc_table_bytes();
 size_t enc_cub_bytes(uint64_t n);
+size_t merge_cub_bytes(uint64_t n);
+hipError_t launch_merge_plan(const MergeParams& P, hipStream_t s);
+hipError_t launch_merge_gather(const GatherParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
+hipError_t launch_index_entries(const EntryParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
 hipError_t launch_read_at(const uint8_t* f, uint64_t len, uint64_t off, uint8_t* out, uint64_t out_cap,
                           ReadAtResult* res, hipStream_t s);
 int build_seek_map(const uint8_t* f, uint64_t len, const uint64_t* rec_off, const uint8_t* flags, uint64_t n,
@@ -219,6 +223,14 @@ struct rio_ctx {
     DevBuf enc_rec, enc_rec_off, enc_flags, enc_out, enc_out_off, enc_len;
     // index search: key prefixes, indices, permutation, radix sort temp
     DevBuf q_pfx, q_pfx_out, q_idx, q_perm, q_tmp;
+    // rio_sst_merge_*: the last plan's views + table bases (device and host copies), key prefixes, scan
+    // input, keep-flag scan, scan temp
+    DevBuf mrg_views, mrg_pfx, mrg_tmp, mrg_opos, mrg_cub;
+    std::vector<uint64_t> mrg_host;
+    uint32_t mrg_T = 0;
+    uint64_t mrg_N = 0;
+    bool mrg_planned = false;
+    hipEvent_t mrg_ev = nullptr;  // recorded after the last plan's copy of mrg_host
     uint8_t* pinned[2] = {nullptr, nullptr};
     hipEvent_t pin_ev[2] = {};
     // device-API calls share the ctx's scratch: a call on another stream than the previous one waits
@@ -406,12 +418,17 @@ extern "C" void rio_ctx_destroy(rio_ctx* c) {
         hipEventSynchronize(c->order_ev);
         hipEventDestroy(c->order_ev);
     }
+    if (c->mrg_ev) {  // the last plan's view copy reads mrg_host
+        hipEventSynchronize(c->mrg_ev);
+        hipEventDestroy(c->mrg_ev);
+    }
     c->fa.release();
     for (auto& a : c->batch) a->release();
     for (DevBuf* b : {&c->sink, &c->file, &c->out, &c->out_off, &c->rec_off, &c->flags,
                       &c->readat_out, &c->readat_res, &c->seek_off, &c->sst_fields, &c->sst_crc, &c->sst_res, &c->sst_view, &c->enc_scr, &c->enc_scr_off, &c->enc_clen, &c->enc_tab,
                       &c->enc_hdr, &c->enc_size, &c->enc_tmp, &c->enc_cub, &c->enc_rec, &c->enc_rec_off, &c->enc_flags, &c->enc_out,
-                      &c->enc_out_off, &c->enc_len, &c->q_pfx, &c->q_pfx_out, &c->q_idx, &c->q_perm, &c->q_tmp})
+                      &c->enc_out_off, &c->enc_len, &c->q_pfx, &c->q_pfx_out, &c->q_idx, &c->q_perm, &c->q_tmp,
+                      &c->mrg_views, &c->mrg_pfx, &c->mrg_tmp, &c->mrg_opos, &c->mrg_cub})
         b->release();
     for (int i = 0; i < 2; i++) {
         if (c->pinned[i]) hipHostFree(c->pinned[i]);
@@ -1555,6 +1572,123 @@ extern "C" int rio_sst_validate_view(rio_ctx* ctx, const uint8_t* d_data_out, co
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
     HIP_TRY(launch_sst_validate(d_data_out, d_data_off, d_data_rec_off, n_data, d_value_off, d_checksum, n_index,
                                 d_crc_out, d_result, s, d_view));
+    return RIO_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// sstables: merge-compaction of loaded tables (rio_compact.hip)
+// ------------------------------------------------------------------------------------------
+extern "C" uint64_t rio_index_entry_len(uint64_t key_len, uint64_t value_offset, uint64_t checksum) {
+    return pb_index_entry_len(key_len, value_offset, checksum);
+}
+
+extern "C" uint64_t rio_index_entries_bound(uint64_t n, uint64_t key_bytes) {
+    // per entry: three tags, the key length (< 2^40: at most 6 bytes) and two 10-byte varints
+    return key_bytes + 29 * n + 64;
+}
+
+// In the three entry points below every argument check stands before the first read of *ctx: a call refused on its
+// arguments touches neither the context nor the device (tests/test_compact_host.py makes such calls on a machine
+// without a GPU, where no context can be created, and passes a placeholder for ctx). Keep that order.
+extern "C" int rio_sst_merge_plan(rio_ctx* ctx, const rio_sst_view* views, uint32_t n_tables, uint32_t mode,
+                                  uint64_t* d_src, uint8_t* d_keep, uint64_t* d_result, void* stream) {
+    if (!ctx || !views || !d_result || n_tables == 0 || n_tables > RIO_MERGE_MAX_TABLES ||
+        mode > RIO_MERGE_LATEST_WINS_SKIP_TOMBSTONES)
+        return RIO_ERR_ARG;
+    static_assert(sizeof(rio_sst_view) % 8 == 0, "views and bases share one uint64 buffer");
+    const size_t vw = sizeof(rio_sst_view) / 8 * n_tables;
+    std::vector<uint64_t> host(vw + n_tables + 1);
+    memcpy(host.data(), views, vw * 8);
+    uint64_t N = 0;
+    for (uint32_t t = 0; t < n_tables; t++) {
+        const rio_sst_view& v = views[t];
+        if (v.n && (!v.index || !v.key_off || !v.key_len || !v.data_off || !v.flags || !v.crc)) return RIO_ERR_ARG;
+        if (v.n >> RIO_MERGE_ENTRY_BITS) return RIO_ERR_UNSUPPORTED;
+        host[vw + t] = N;
+        N += v.n;
+    }
+    host[vw + n_tables] = N;
+    if (N >= (1ull << 31) - 1) return RIO_ERR_UNSUPPORTED;
+    if (N && (!d_src || !d_keep)) return RIO_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    ctx->mrg_planned = false;
+    HIP_TRY(ctx->mrg_views.ensure(host.size() * 8));
+    HIP_TRY(ctx->mrg_pfx.ensure(N * 8 + 8));
+    HIP_TRY(ctx->mrg_tmp.ensure(N * 8 + 8));
+    HIP_TRY(ctx->mrg_opos.ensure(N * 8 + 8));
+    HIP_TRY(ctx->mrg_cub.ensure(std::max<size_t>(merge_cub_bytes(N), 256)));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    // the host copy lives in the context until the next plan, which waits for this plan's copy of it (not
+    // for the stream): the copy may read it after this call returns
+    if (!ctx->mrg_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->mrg_ev, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(ctx->mrg_ev));
+    ctx->mrg_host.swap(host);
+    HIP_TRY(hipMemcpyAsync(ctx->mrg_views.p, ctx->mrg_host.data(), ctx->mrg_host.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(ctx->mrg_ev, s));
+    MergeParams P{};
+    P.views = ctx->mrg_views.as<rio_sst_view>();
+    P.base = ctx->mrg_views.as<uint64_t>() + vw;
+    P.T = n_tables;
+    P.mode = mode;
+    P.N = N;
+    P.pfx = ctx->mrg_pfx.as<uint64_t>();
+    P.src = d_src;
+    P.keep = d_keep;
+    P.result = d_result;
+    HIP_TRY(launch_merge_plan(P, s));
+    ctx->mrg_T = n_tables;
+    ctx->mrg_N = N;
+    ctx->mrg_planned = true;
+    return RIO_OK;
+}
+
+extern "C" int rio_sst_merge_gather(rio_ctx* ctx, const uint64_t* d_src, const uint8_t* d_keep, uint64_t n_out,
+                                    uint64_t* d_out_src, uint8_t* d_values, uint64_t values_cap, uint64_t* d_val_off,
+                                    uint8_t* d_val_flags, void* stream) {
+    if (!ctx || !d_val_off || !d_values || (n_out && (!d_out_src || !d_val_flags))) return RIO_ERR_ARG;
+    // from here on *ctx is read
+    if (!ctx->mrg_planned) return RIO_ERR_STATE;
+    if (n_out > ctx->mrg_N || (ctx->mrg_N && (!d_src || !d_keep))) return RIO_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    GatherParams P{};
+    P.views = ctx->mrg_views.as<rio_sst_view>();
+    P.T = ctx->mrg_T;
+    P.N = ctx->mrg_N;
+    P.n_out = n_out;
+    P.src = d_src;
+    P.keep = d_keep;
+    P.tmp = ctx->mrg_tmp.as<uint64_t>();
+    P.opos = ctx->mrg_opos.as<uint64_t>();
+    P.out_src = d_out_src;
+    P.values = d_values;
+    P.values_cap = values_cap;
+    P.val_off = d_val_off;
+    P.val_flags = d_val_flags;
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    HIP_TRY(launch_merge_gather(P, ctx->mrg_cub.p, ctx->mrg_cub.cap, s));
+    return RIO_OK;
+}
+
+extern "C" int rio_sst_index_encode(rio_ctx* ctx, const uint64_t* d_out_src, const uint64_t* d_value_file_off,
+                                    uint64_t n_out, uint8_t* d_entries, uint64_t entries_cap, uint64_t* d_ent_off,
+                                    void* stream) {
+    if (!ctx || !d_ent_off || !d_entries || (n_out && (!d_out_src || !d_value_file_off))) return RIO_ERR_ARG;
+    // from here on *ctx is read
+    if (!ctx->mrg_planned) return RIO_ERR_STATE;
+    if (n_out > ctx->mrg_N) return RIO_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    EntryParams P{};
+    P.views = ctx->mrg_views.as<rio_sst_view>();
+    P.T = ctx->mrg_T;
+    P.n_out = n_out;
+    P.out_src = d_out_src;
+    P.file_off = d_value_file_off;
+    P.tmp = ctx->mrg_tmp.as<uint64_t>();
+    P.entries = d_entries;
+    P.entries_cap = entries_cap;
+    P.ent_off = d_ent_off;
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    HIP_TRY(launch_index_entries(P, ctx->mrg_cub.p, ctx->mrg_cub.cap, s));
     return RIO_OK;
 }
 

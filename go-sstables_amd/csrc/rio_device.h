@@ -184,6 +184,64 @@ struct EncParams {
     uint32_t lds_small;        // records <= 1 KiB on the LDS-table kernel
 };
 
+// rio_compact.hip: merge-compaction of loaded tables (rio_sst_merge_plan / _gather, rio_sst_index_encode)
+struct MergeParams {
+    const rio_sst_view* views;  // [T] device copy of the caller's views
+    const uint64_t* base;       // [T + 1] number of table t's first entry among all N input entries
+    uint32_t T;
+    uint32_t mode;              // RIO_MERGE_*
+    uint64_t N;
+    uint64_t* pfx;              // [N] first 8 key bytes, big-endian, zero-padded
+    uint64_t* src;              // [N] table << RIO_MERGE_ENTRY_BITS | entry, in merged order
+    uint8_t* keep;              // [N]
+    uint64_t* result;           // [RIO_MERGE_RESULT_WORDS]
+};
+struct GatherParams {
+    const rio_sst_view* views;
+    uint32_t T;
+    uint64_t N, n_out;
+    const uint64_t* src;        // [N] the plan's order
+    const uint8_t* keep;        // [N]
+    uint64_t* tmp;              // [max(N, n_out) + 1] scan input
+    uint64_t* opos;             // [N + 1] exclusive scan of keep
+    uint64_t* out_src;          // [n_out]
+    uint8_t* values;
+    uint64_t values_cap;
+    uint64_t* val_off;          // [n_out + 1]
+    uint8_t* val_flags;         // [n_out]
+};
+struct EntryParams {
+    const rio_sst_view* views;
+    uint32_t T;
+    uint64_t n_out;
+    const uint64_t* out_src;    // [n_out]
+    const uint64_t* file_off;   // [n_out] ValueOffset of each entry
+    uint64_t* tmp;              // [n_out + 1] scan input
+    uint8_t* entries;
+    uint64_t entries_cap;
+    uint64_t* ent_off;          // [n_out + 1]
+};
+
+// protobuf varint length, and proto.Marshal's size of an IndexEntry {key = 1, valueOffset = 2, checksum = 3}:
+// proto3 omits an empty key and zero scalars (sstables/proto/sstable.proto:5-9)
+#ifdef __HIPCC__
+#define RIO_HD __host__ __device__
+#else
+#define RIO_HD
+#endif
+RIO_HD inline uint32_t pb_varint_len(uint64_t v) {
+    uint32_t n = 1;
+    while (v >= 0x80) {
+        v >>= 7;
+        n++;
+    }
+    return n;
+}
+RIO_HD inline uint64_t pb_index_entry_len(uint64_t key_len, uint64_t value_off, uint64_t checksum) {
+    return (key_len ? 1 + pb_varint_len(key_len) + key_len : 0) + (value_off ? 1 + pb_varint_len(value_off) : 0) +
+           (checksum ? 1 + pb_varint_len(checksum) : 0);
+}
+
 #ifdef __HIPCC__
 // A record whose payload does not decode: flag it for ReadNext (RIO_FLAG_CORRUPT) and count it.
 // Only the thread that decoded record i writes its flag byte.

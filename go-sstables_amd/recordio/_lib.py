@@ -88,6 +88,31 @@ class SstInfo(ctypes.Structure):
     ]
 
 
+RIO_MERGE_MAX_TABLES = 256
+RIO_MERGE_ENTRY_BITS = 40
+RIO_MERGE_ALL, RIO_MERGE_LATEST_WINS, RIO_MERGE_LATEST_WINS_SKIP_TOMBSTONES = 0, 1, 2
+RIO_MERGE_RESULT_WORDS = 8
+(RIO_MERGE_R_N_OUT, RIO_MERGE_R_VALUE_BYTES, RIO_MERGE_R_NULL_VALUES, RIO_MERGE_R_FIRST_DUP, RIO_MERGE_R_UNSORTED,
+ RIO_MERGE_R_KEY_BYTES) = range(6)
+
+
+class SstView(ctypes.Structure):
+    """rio_sst_view (include/rio.h): one loaded table's device arrays."""
+
+    _fields_ = [
+        ("index", c_void_p),
+        ("key_off", c_void_p),
+        ("key_len", c_void_p),
+        ("data", c_void_p),
+        ("data_off", c_void_p),
+        ("flags", c_void_p),
+        ("crc", c_void_p),
+        ("n", c_uint64),
+        ("index_bytes", c_uint64),
+        ("data_bytes", c_uint64),
+    ]
+
+
 class IndexHit(ctypes.Structure):
     """rio_index_hit (include/rio.h)."""
 
@@ -209,6 +234,12 @@ _SIGS = {
     "rio_index_open": (c_int, [c_void_p, c_void_p, c_uint64, POINTER(c_void_p)]),
     "rio_index_search": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p]),
     "rio_index_free": (None, [c_void_p]),
+    "rio_sst_merge_plan": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rio_sst_merge_gather": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p]),
+    "rio_sst_index_encode": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p]),
+    "rio_index_entry_len": (c_uint64, [c_uint64, c_uint64, c_uint64]),
+    "rio_index_entries_bound": (c_uint64, [c_uint64, c_uint64]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -373,3 +373,7 @@ def NewSSTableReader(*options):  # noqa: N802
         return None, GoError(f"validateDataFile error loading value '{o.basePath}' at key "
                              f"[{_fmt_key(t.key(i))}]: {e}", wrapped=e)
     return r, None
+
+
+from .merger import (NewSSTableMerger, ScanReduceLatestWins, ScanReduceLatestWinsSkipTombstones,  # noqa: E402,F401
+                     SSTableMerger)

@@ -329,6 +329,89 @@ int rio_device_encode(rio_ctx* ctx, const uint8_t* d_records, const uint64_t* d_
 int rio_encode_file(rio_ctx* ctx, const uint8_t* records, const uint64_t* rec_off, const uint8_t* flags, uint64_t n,
                     uint32_t compression, uint8_t* out, uint64_t out_cap, uint64_t* out_rec_off, uint64_t* out_len);
 
+/* ---- merge-compaction of loaded tables on the device (rio_compact.hip) -----------------------
+ * Replaces SSTableMerger.Merge / MergeCompact / MergeCompactIterator (sstables/sstable_merger.go:36-169:
+ * a priority queue over T scan iterators, one WriteNext per surviving key) with the reducers
+ * ScanReduceLatestWins / ScanReduceLatestWinsSkipTombstones (super_sstable_reader.go:107-131, what
+ * simpledb/compaction.go:119 runs for every compaction), and the IndexEntry side of
+ * SSTableStreamWriter.WriteNext (sstable_writer.go:98-150). Everything works on the device arrays a
+ * table load leaves behind (rio_device_decode of both files, rio_sst_index_parse, rio_sst_validate).
+ * Table t of a call is views[t]; its position in the array is the reducer's context (the position
+ * SuperSSTableReader.Scan assigns, super_sstable_reader.go:88-97): the highest position wins.
+ * Limits: 1 <= T <= RIO_MERGE_MAX_TABLES, entries per table < 2^40, entries of all tables < 2^31
+ * (RIO_ERR_UNSUPPORTED beyond). Bytes comparator only (skiplist.BytesComparator: lexicographic,
+ * unsigned, a proper prefix first).
+ *
+ * The three calls are one sequence on one context: rio_sst_merge_plan copies the views to the
+ * context and sizes the context's merge scratch (prefixes, scan inputs and outputs, scan temp: about
+ * 40 bytes per input entry) for all three; rio_sst_merge_gather and rio_sst_index_encode work on the
+ * last plan's views and allocate nothing. Outputs are caller buffers. All three are stream-ordered
+ * (NULL = the ctx stream) and never wait for the stream (a plan waits only for the previous plan's copy
+ * of its views, a host array, so the plan is not graph-capturable). The caller reads d_result (64 bytes) after the plan:
+ * rio_device_encode takes its record count by value, so n_out must be known on the host; that copy
+ * is the sequence's only host round trip before the output files are fetched. */
+#define RIO_MERGE_MAX_TABLES 256u
+#define RIO_MERGE_ENTRY_BITS 40u /* src = table << RIO_MERGE_ENTRY_BITS | entry */
+#define RIO_MERGE_ALL 0u                          /* SSTableMerger.Merge: every entry, nil values too */
+#define RIO_MERGE_LATEST_WINS 1u                  /* MergeCompact + ScanReduceLatestWins */
+#define RIO_MERGE_LATEST_WINS_SKIP_TOMBSTONES 2u  /* MergeCompact + ScanReduceLatestWinsSkipTombstones */
+typedef struct rio_sst_view {
+    const uint8_t* index;      /* decoded index arena (rio_device_decode of index.rio) */
+    const uint64_t* key_off;   /* [n] key i = index[key_off[i] .. + key_len[i]) (rio_sst_index_parse) */
+    const uint64_t* key_len;   /* [n] */
+    const uint8_t* data;       /* decoded data arena (rio_device_decode of data.rio) */
+    const uint64_t* data_off;  /* [n + 1] value i = data[data_off[i] .. data_off[i + 1]) */
+    const uint8_t* flags;      /* [n] RIO_FLAG_NIL marks a nil value */
+    const uint64_t* crc;       /* [n] CRC-64/ISO of value i (rio_sst_validate's d_crc_out) */
+    uint64_t n;                /* entries */
+    uint64_t index_bytes;      /* length of the index arena: keys are clamped to it */
+    uint64_t data_bytes;       /* length of the data arena: values are clamped to it */
+} rio_sst_view;
+/* d_result of rio_sst_merge_plan (uint64[RIO_MERGE_RESULT_WORDS]) */
+#define RIO_MERGE_RESULT_WORDS 8u
+#define RIO_MERGE_R_N_OUT 0u        /* surviving entries */
+#define RIO_MERGE_R_VALUE_BYTES 1u  /* their value bytes */
+#define RIO_MERGE_R_NULL_VALUES 2u  /* survivors with a nil value (MetaData.nullValues; RIO_MERGE_ALL only) */
+#define RIO_MERGE_R_FIRST_DUP 3u    /* RIO_MERGE_ALL: first merged position whose key equals its predecessor's
+                                       (WriteNext's "the same key cannot be written more than once"); ~0 = none */
+#define RIO_MERGE_R_UNSORTED 4u     /* first table whose keys are not strictly ascending, or whose key / value
+                                       ranges leave their arenas; ~0 = none. Nothing else of the plan is
+                                       meaningful then (the caller returns RIO_ERR_UNSUPPORTED): merged
+                                       positions can collide, so d_src and d_keep may be partly unwritten */
+#define RIO_MERGE_R_KEY_BYTES 5u    /* key bytes of the survivors (sizes rio_sst_index_encode's output) */
+/* Plan: order all N = sum of views[t].n entries by (key, table position) and decide survival.
+ *   d_src  [N] entry at merged position p = views[d_src[p] >> 40] entry (d_src[p] & (2^40 - 1))
+ *   d_keep [N] 1 when position p survives the mode's reduce
+ * Each table's order is checked, not trusted: every search and every later gather index is clamped
+ * to its table and arena, so an unsorted or inconsistent input yields RIO_MERGE_R_UNSORTED, never an
+ * out-of-range access. Returns RIO_ERR_ARG for NULL views / outputs, T = 0, T > RIO_MERGE_MAX_TABLES
+ * or an unknown mode, before any device call. */
+int rio_sst_merge_plan(rio_ctx* ctx, const rio_sst_view* views, uint32_t n_tables, uint32_t mode, uint64_t* d_src,
+                       uint8_t* d_keep, uint64_t* d_result, void* stream);
+/* Gather of the last plan's survivors (n_out = d_result[RIO_MERGE_R_N_OUT], read by the caller) into
+ * the layout rio_device_encode takes:
+ *   d_out_src   [n_out]      the survivors' d_src words in merged order
+ *   d_values    [values_cap] values back to back; values_cap >= value bytes + RIO_DEVICE_PAD
+ *   d_val_off   [n_out + 1]  value j = d_values[d_val_off[j] .. d_val_off[j + 1])
+ *   d_val_flags [n_out]      RIO_FLAG_NIL for a nil value
+ * A value that would pass values_cap is not copied. RIO_ERR_STATE without a plan on this context. */
+int rio_sst_merge_gather(rio_ctx* ctx, const uint64_t* d_src, const uint8_t* d_keep, uint64_t n_out,
+                         uint64_t* d_out_src, uint8_t* d_values, uint64_t values_cap, uint64_t* d_val_off,
+                         uint8_t* d_val_flags, void* stream);
+/* Index records of the output table: entry j = proto.Marshal(&IndexEntry{Key, ValueOffset, Checksum})
+ * (sstable_writer.go:126-132; proto3: an empty key, offset 0 and checksum 0 are omitted, varints are
+ * minimal) with the key and the CRC-64 of survivor d_out_src[j] (the value is not hashed again) and
+ * ValueOffset = d_value_file_off[j], the record offsets rio_device_encode returned for the values.
+ *   d_entries [entries_cap]  entries back to back; entries_cap >= rio_index_entries_bound(n_out, key bytes)
+ *   d_ent_off [n_out + 1]
+ * An entry that would pass entries_cap is not written. The arena and offsets then go to
+ * rio_device_encode(RIO_COMP_NONE) for index.rio. */
+int rio_sst_index_encode(rio_ctx* ctx, const uint64_t* d_out_src, const uint64_t* d_value_file_off, uint64_t n_out,
+                         uint8_t* d_entries, uint64_t entries_cap, uint64_t* d_ent_off, void* stream);
+/* host helpers: the marshalled length of one IndexEntry, and the arena bound for n of them */
+uint64_t rio_index_entry_len(uint64_t key_len, uint64_t value_offset, uint64_t checksum);
+uint64_t rio_index_entries_bound(uint64_t n, uint64_t key_bytes);
+
 /* ---- DiskKeyIndex lookups (sstables/disk_key_index.go:87-140) --------------------------------
  * Batched DiskKeyIndex.Get / Contains / IteratorStartingAt: one result per query key, each the
  * reference's binarySearch over the byte offsets of an uncompressed index.rio with every probe
