@@ -61,6 +61,8 @@ size_t merge_cub_bytes(uint64_t n);
 hipError_t launch_merge_plan(const MergeParams& P, hipStream_t s);
 hipError_t launch_merge_gather(const GatherParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
 hipError_t launch_index_entries(const EntryParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
+size_t flush_cub_bytes(uint64_t n, uint32_t max_key_len);
+hipError_t launch_flush_plan(const FlushParams& P, hipStream_t s, hipEvent_t* ev, uint32_t* n_stages);
 hipError_t launch_read_at(const uint8_t* f, uint64_t len, uint64_t off, uint8_t* out, uint64_t out_cap,
                           ReadAtResult* res, hipStream_t s);
 int build_seek_map(const uint8_t* f, uint64_t len, const uint64_t* rec_off, const uint8_t* flags, uint64_t n,
@@ -231,6 +233,11 @@ struct rio_ctx {
     uint64_t mrg_N = 0;
     bool mrg_planned = false;
     hipEvent_t mrg_ev = nullptr;  // recorded after the last plan's copy of mrg_host
+    // rio_sst_flush_plan: key lengths and value CRCs (the registered view's arrays, alive until the next plan),
+    // digits (2 x n), permutations (2 x n), radix sort temp; stage events while timing is on
+    DevBuf fl_len, fl_crc, fl_dig, fl_perm, fl_cub;
+    std::vector<hipEvent_t> fl_ev;
+    uint32_t fl_stages = 0;
     uint8_t* pinned[2] = {nullptr, nullptr};
     hipEvent_t pin_ev[2] = {};
     // device-API calls share the ctx's scratch: a call on another stream than the previous one waits
@@ -428,8 +435,10 @@ extern "C" void rio_ctx_destroy(rio_ctx* c) {
                       &c->readat_out, &c->readat_res, &c->seek_off, &c->sst_fields, &c->sst_crc, &c->sst_res, &c->sst_view, &c->enc_scr, &c->enc_scr_off, &c->enc_clen, &c->enc_tab,
                       &c->enc_hdr, &c->enc_size, &c->enc_tmp, &c->enc_cub, &c->enc_rec, &c->enc_rec_off, &c->enc_flags, &c->enc_out,
                       &c->enc_out_off, &c->enc_len, &c->q_pfx, &c->q_pfx_out, &c->q_idx, &c->q_perm, &c->q_tmp,
-                      &c->mrg_views, &c->mrg_pfx, &c->mrg_tmp, &c->mrg_opos, &c->mrg_cub})
+                      &c->mrg_views, &c->mrg_pfx, &c->mrg_tmp, &c->mrg_opos, &c->mrg_cub, &c->fl_len, &c->fl_crc, &c->fl_dig,
+                      &c->fl_perm, &c->fl_cub})
         b->release();
+    for (hipEvent_t e : c->fl_ev) hipEventDestroy(e);
     for (int i = 0; i < 2; i++) {
         if (c->pinned[i]) hipHostFree(c->pinned[i]);
         if (c->pin_ev[i]) hipEventDestroy(c->pin_ev[i]);
@@ -1690,6 +1699,99 @@ extern "C" int rio_sst_index_encode(rio_ctx* ctx, const uint64_t* d_out_src, con
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
     HIP_TRY(launch_index_entries(P, ctx->mrg_cub.p, ctx->mrg_cub.cap, s));
     return RIO_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// memstore flush: order an op log and keep the latest op of every key (rio_flush.hip)
+// ------------------------------------------------------------------------------------------
+// As for the merge entry points: every argument check stands before the first read of *ctx
+// (tests/test_memstore_host.py calls this with a placeholder ctx on a machine without a GPU).
+extern "C" int rio_sst_flush_plan(rio_ctx* ctx, const rio_ops_view* ops, uint32_t mode, uint32_t max_key_len,
+                                  uint64_t* d_src, uint8_t* d_keep, uint64_t* d_result, void* stream) {
+    if (!ctx || !ops || !d_result || mode > RIO_FLUSH_SKIP_TOMBSTONES) return RIO_ERR_ARG;
+    const uint64_t n = ops->n;
+    if (n && (!ops->keys || !ops->key_off || !ops->values || !ops->val_off || !ops->flags || !d_src || !d_keep))
+        return RIO_ERR_ARG;
+    if (n >= (1ull << 31) - 1 || max_key_len > RIO_FLUSH_MAX_KEY_LEN) return RIO_ERR_UNSUPPORTED;
+    // from here on *ctx is read
+    HIP_TRY(hipSetDevice(ctx->device));
+    ctx->mrg_planned = false;
+    // the one-table view of the log the gather and the index encode work on, then its bases {0, n}
+    constexpr size_t vw = sizeof(rio_sst_view) / 8;
+    std::vector<uint64_t> host(vw + 2);
+    HIP_TRY(ctx->mrg_views.ensure(host.size() * 8));
+    HIP_TRY(ctx->mrg_tmp.ensure(n * 8 + 8));
+    HIP_TRY(ctx->mrg_opos.ensure(n * 8 + 8));
+    HIP_TRY(ctx->mrg_cub.ensure(std::max<size_t>(merge_cub_bytes(n), 256)));
+    HIP_TRY(ctx->fl_len.ensure(n * 8 + 8));
+    HIP_TRY(ctx->fl_crc.ensure(n * 8 + 8));
+    HIP_TRY(ctx->fl_dig.ensure(2 * n * 8 + 16));
+    HIP_TRY(ctx->fl_perm.ensure(2 * n * 4 + 16));
+    HIP_TRY(ctx->fl_cub.ensure(std::max<size_t>(flush_cub_bytes(n, max_key_len), 256)));
+    rio_sst_view v{};
+    v.index = ops->keys;
+    v.key_off = ops->key_off;
+    v.key_len = ctx->fl_len.as<uint64_t>();
+    v.data = ops->values;
+    v.data_off = ops->val_off;
+    v.flags = ops->flags;
+    v.crc = ctx->fl_crc.as<uint64_t>();
+    v.n = n;
+    v.index_bytes = ops->key_bytes;
+    v.data_bytes = ops->value_bytes;
+    memcpy(host.data(), &v, sizeof v);
+    host[vw] = 0;
+    host[vw + 1] = n;
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    // as rio_sst_merge_plan: the host copy lives in the context until the next plan, which waits for this
+    // plan's copy of it, not for the stream
+    if (!ctx->mrg_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->mrg_ev, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(ctx->mrg_ev));
+    ctx->mrg_host.swap(host);
+    HIP_TRY(hipMemcpyAsync(ctx->mrg_views.p, ctx->mrg_host.data(), ctx->mrg_host.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(ctx->mrg_ev, s));
+    hipEvent_t* ev = nullptr;
+    if (!ctx->ev.empty()) {  // rio_ctx_set_timing: stage events (rio_sst_flush_stage_ms)
+        while (ctx->fl_ev.size() < kFlushMaxStages + 1) {
+            hipEvent_t e;
+            HIP_TRY(hipEventCreate(&e));
+            ctx->fl_ev.push_back(e);
+        }
+        ev = ctx->fl_ev.data();
+    }
+    FlushParams P{};
+    P.ops = *ops;
+    P.mode = mode;
+    P.max_key_len = max_key_len;
+    P.key_len = ctx->fl_len.as<uint64_t>();
+    P.crc = ctx->fl_crc.as<uint64_t>();
+    P.dig[0] = ctx->fl_dig.as<uint64_t>();
+    P.dig[1] = P.dig[0] + n + 1;
+    P.perm[0] = ctx->fl_perm.as<uint32_t>();
+    P.perm[1] = P.perm[0] + n + 1;
+    P.cub = ctx->fl_cub.p;
+    P.cub_bytes = ctx->fl_cub.cap;
+    P.src = d_src;
+    P.keep = d_keep;
+    P.result = d_result;
+    ctx->fl_stages = 0;
+    uint32_t stages = 0;
+    HIP_TRY(launch_flush_plan(P, s, ev, &stages));
+    ctx->fl_stages = ev ? stages : 0;
+    ctx->mrg_T = 1;
+    ctx->mrg_N = n;
+    ctx->mrg_planned = true;
+    return RIO_OK;
+}
+
+extern "C" int rio_sst_flush_stage_ms(rio_ctx* ctx, float* ms, int n) {
+    if (!ctx || !ms || n <= 0) return 0;
+    const uint32_t k = std::min<uint32_t>(ctx->fl_stages, (uint32_t)n);
+    if (!k || ctx->fl_ev.size() < (size_t)ctx->fl_stages + 1) return 0;
+    if (hipEventSynchronize(ctx->fl_ev[ctx->fl_stages]) != hipSuccess) return 0;
+    for (uint32_t i = 0; i < k; i++)
+        if (hipEventElapsedTime(&ms[i], ctx->fl_ev[i], ctx->fl_ev[i + 1]) != hipSuccess) return 0;
+    return (int)k;
 }
 
 // ------------------------------------------------------------------------------------------

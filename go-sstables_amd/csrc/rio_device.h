@@ -222,6 +222,23 @@ struct EntryParams {
     uint64_t* ent_off;          // [n_out + 1]
 };
 
+// rio_flush.hip: ordering and latest-wins reduce of a memstore's op log (rio_sst_flush_plan)
+struct FlushParams {
+    rio_ops_view ops;
+    uint32_t mode;              // RIO_FLUSH_*
+    uint32_t max_key_len;       // bound on the key lengths: ceil(max_key_len / 8) chunk passes
+    uint64_t* key_len;          // [n] clamped key lengths (the registered view's key_len)
+    uint64_t* crc;              // [n] CRC-64/ISO of the kept values, by op (the registered view's crc)
+    uint64_t* dig[2];           // [n] a pass's digits and the sort's reordered copy of them
+    uint32_t* perm[2];          // [n] op indices in the order so far, in and out of a pass
+    void* cub;                  // radix sort temp
+    size_t cub_bytes;
+    uint64_t* src;              // [n] op at sorted position p
+    uint8_t* keep;              // [n]
+    uint64_t* result;           // [RIO_MERGE_RESULT_WORDS]
+};
+constexpr uint32_t kFlushMaxStages = (RIO_FLUSH_MAX_KEY_LEN + 7) / 8 + 1 + 3;  // check, passes, keep, crc
+
 // protobuf varint length, and proto.Marshal's size of an IndexEntry {key = 1, valueOffset = 2, checksum = 3}:
 // proto3 omits an empty key and zero scalars (sstables/proto/sstable.proto:5-9)
 #ifdef __HIPCC__

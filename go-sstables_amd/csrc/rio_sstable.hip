@@ -29,6 +29,7 @@
 //                k_sst_validate then hashes these ranges instead of the whole records.
 #include <hip/hip_runtime.h>
 
+#include "rio_crc64.h"
 #include "rio_device.h"
 #include "rio_dev_util.h"
 #include "rio_pb.h"
@@ -51,14 +52,6 @@ __global__ void __launch_bounds__(256) k_sst_index(const uint8_t* arena, const u
         checksum[i] = cs;
         if (!ok) atomicMin(first_bad, (unsigned long long)i);
     }
-}
-
-// CRC-64/ISO, reflected, slice-by-8: tab[k][i] = CRC of byte i followed by k zero bytes, so one
-// 8-byte step is eight independent LDS lookups instead of eight dependent ones.
-__device__ __forceinline__ uint64_t crc64_step8(const uint64_t (*tab)[256], uint64_t c, uint64_t w) {
-    c ^= w;
-    return tab[7][c & 0xFF] ^ tab[6][(c >> 8) & 0xFF] ^ tab[5][(c >> 16) & 0xFF] ^ tab[4][(c >> 24) & 0xFF] ^
-           tab[3][(c >> 32) & 0xFF] ^ tab[2][(c >> 40) & 0xFF] ^ tab[1][(c >> 48) & 0xFF] ^ tab[0][c >> 56];
 }
 
 __global__ void __launch_bounds__(256) k_sst_data_entry(const uint8_t* arena, const uint64_t* off, uint64_t n,
@@ -84,17 +77,7 @@ __global__ void __launch_bounds__(256) k_sst_validate(const uint8_t* data, const
                                                       uint64_t n_index, uint64_t* crc_out,
                                                       unsigned long long* result, const uint64_t* view) {
     __shared__ uint64_t tab[8][256];  // 16 KiB
-    for (uint32_t k = threadIdx.x; k < 256; k += blockDim.x) {
-        uint64_t c = k;
-        for (int j = 0; j < 8; j++) c = (c >> 1) ^ (0xD800000000000000ull & (0ull - (c & 1ull)));
-        tab[0][k] = c;
-    }
-    __syncthreads();
-    for (int t = 1; t < 8; t++) {
-        for (uint32_t k = threadIdx.x; k < 256; k += blockDim.x)
-            tab[t][k] = (tab[t - 1][k] >> 8) ^ tab[0][tab[t - 1][k] & 0xFF];
-        __syncthreads();
-    }
+    crc64_build_table(tab);
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_index; i += stride) {
         const uint64_t want = value_off[i];
@@ -122,27 +105,7 @@ __global__ void __launch_bounds__(256) k_sst_validate(const uint8_t* data, const
             ve = view[2 * j + 1];
             if (vb >= RIO_VALUE_BAD) vb = ve = 0;
         }
-        const uint8_t* v = data + vb;
-        const uint64_t len = ve - vb;
-        uint64_t c = ~0ull, k = 0;
-        // 64 bytes per iteration: four unaligned 16-byte loads in flight before the CRC steps
-        for (; k + 64 <= len; k += 64) {
-            uint4 w[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++) w[q] = ldu16(v + k + 16 * q);
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                c = crc64_step8(tab, c, ((uint64_t)w[q].y << 32) | w[q].x);
-                c = crc64_step8(tab, c, ((uint64_t)w[q].w << 32) | w[q].z);
-            }
-        }
-        for (; k + 16 <= len; k += 16) {
-            const uint4 w = ldu16(v + k);
-            c = crc64_step8(tab, c, ((uint64_t)w.y << 32) | w.x);
-            c = crc64_step8(tab, c, ((uint64_t)w.w << 32) | w.z);
-        }
-        for (; k < len; k++) c = tab[0][(c ^ v[k]) & 0xFFu] ^ (c >> 8);
-        c = ~c;
+        const uint64_t c = crc64_value(tab, data + vb, ve - vb);
         crc_out[i] = c;
         if (checksum[i] != 0 && c != checksum[i]) atomicMin(&result[0], (unsigned long long)i);
     }

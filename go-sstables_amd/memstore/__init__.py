@@ -1,0 +1,228 @@
+"""MemStore mirror (memstore/memstore.go) whose flush runs on the device.
+
+Point semantics (Add / Get / Upsert / Delete / Tombstone, the size estimate) live in a host dict from key
+to its latest value. Every mutating call also appends to an op log: a key arena, a value arena, offsets and
+flags, in application order and not deduplicated. Flush / FlushWithTombstones ship the log and run
+rio_sst_flush_plan (rio_flush.hip: order by (key, op index), keep the latest op of every key, drop nil
+ones under Flush), then the back end merge-compaction uses (sstables.merger.encode_planned: gather, data
+encode, index entries, index encode). The three files are byte-identical to what the reference's
+SSTableStreamWriter writes for the same sorted pairs. None is Go's nil; b"" is an empty non-nil key or
+value. Functions return Go-style error values. There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes
+import struct
+
+from recordio import _lib as L
+from recordio.errors import GoError
+
+KeyAlreadyExists = GoError("key already exists")  # memstore.go:10-14
+KeyNotFound = GoError("key not found")
+KeyTombstoned = GoError("key was tombstoned")
+KeyNil = GoError("key was nil")
+ValueNil = GoError("value was nil")
+
+_NONE = 0xFFFFFFFFFFFFFFFF
+
+
+def _key(key) -> bytes:
+    return b"" if key is None else bytes(key)  # a nil []byte compares as the empty key
+
+
+def _f32(x: float) -> float:
+    return struct.unpack("f", struct.pack("f", x))[0]
+
+
+def flush_ops_on_device(ctx, device: int, ops_view, mode: int, comp: int, mark=None,
+                        max_key_len: int = L.RIO_FLUSH_MAX_KEY_LEN):
+    """rio_sst_flush_plan over a device-resident op log (an OpsView), then gather, data encode, index
+    entries and index encode on torch's current stream; returns the merger's Compaction (status "unsorted"
+    with unsorted_table = the first rejected op when the log is inconsistent or a key is longer than
+    max_key_len). max_key_len bounds the key lengths and sets the sort's pass count: pass the longest key's
+    length. `mark(name)` as for sstables.merger.compact_on_device."""
+    import torch
+
+    from sstables.merger import check_status, encode_planned, on_device_stream
+
+    mark = mark or (lambda name: None)
+    dev = f"cuda:{device}"
+    n = int(ops_view.n)
+
+    def run(st):
+        src = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        keep = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        res = torch.empty(L.RIO_MERGE_RESULT_WORDS, dtype=torch.int64, device=dev)
+        check_status(L.lib().rio_sst_flush_plan(ctx, ctypes.addressof(ops_view), mode, max_key_len, src.data_ptr(),
+                                          keep.data_ptr(), res.data_ptr(), st), "rio_sst_flush_plan")
+        mark("plan")
+        return encode_planned(ctx, device, st, src, keep, res, comp, mark, False)
+
+    return on_device_stream(device, run)
+
+
+class _Iterator:
+    """SkipListSStableIterator (memstore/sstable_iterator.go): keys ascending, nil for a tombstoned key."""
+
+    def __init__(self, items):
+        self.items, self.i = items, 0
+
+    def Next(self):  # noqa: N802
+        from sstables import Done
+
+        if self.i >= len(self.items):
+            return None, None, Done
+        k, v = self.items[self.i]
+        self.i += 1
+        return k, v, None
+
+
+class MemStore:
+    def __init__(self, device: int = 0):
+        self.device = device
+        self._latest = {}  # key -> latest value, None when tombstoned
+        self._size = 0     # estimatedSize
+        # the op log
+        self._keys, self._values = bytearray(), bytearray()
+        self._key_off, self._val_off = [0], [0]
+        self._flags = bytearray()
+        self._max_key_len = 0
+
+    def _log(self, key: bytes, value):
+        self._keys += key
+        self._key_off.append(len(self._keys))
+        if value is not None:
+            self._values += value
+        self._val_off.append(len(self._values))
+        self._flags.append(L.RIO_FLAG_NIL if value is None else 0)
+        self._max_key_len = max(self._max_key_len, len(key))
+
+    def _upsert(self, key, value, error_if_exists: bool):
+        if key is None:
+            return KeyNil
+        if value is None:
+            return ValueNil
+        key, value = bytes(key), bytes(value)
+        if key in self._latest:
+            prev = self._latest[key]
+            if prev is not None and error_if_exists:
+                return KeyAlreadyExists
+            self._size += len(value) - (0 if prev is None else len(prev))
+        else:
+            self._size += len(key) + len(value)
+        self._latest[key] = value
+        self._log(key, value)
+        return None
+
+    def Add(self, key, value):  # noqa: N802
+        return self._upsert(key, value, True)
+
+    def Upsert(self, key, value):  # noqa: N802
+        return self._upsert(key, value, False)
+
+    def Contains(self, key) -> bool:  # noqa: N802
+        return self._latest.get(_key(key)) is not None
+
+    def IsTombstoned(self, key) -> bool:  # noqa: N802
+        key = _key(key)
+        return key in self._latest and self._latest[key] is None
+
+    def Get(self, key):  # noqa: N802
+        key = _key(key)
+        if key not in self._latest:
+            return None, KeyNotFound
+        v = self._latest[key]
+        if v is None:
+            return None, KeyTombstoned
+        return v, None
+
+    def _delete(self, key, error_if_not_found: bool):
+        key = _key(key)
+        if key not in self._latest:
+            return KeyNotFound if error_if_not_found else None
+        prev = self._latest[key]
+        self._size -= 0 if prev is None else len(prev)
+        self._latest[key] = None
+        self._log(key, None)
+        return None
+
+    def Delete(self, key):  # noqa: N802
+        return self._delete(key, True)
+
+    def DeleteIfExists(self, key):  # noqa: N802
+        return self._delete(key, False)
+
+    def Tombstone(self, key):  # noqa: N802
+        key = _key(key)
+        if key in self._latest:
+            return self._delete(key, False)
+        self._latest[key] = None
+        self._size += len(key)
+        self._log(key, None)
+        return None
+
+    def EstimatedSizeInBytes(self) -> int:  # noqa: N802
+        # uint64(1.15 * float32(m.estimatedSize)): the product of two float32 values, rounded to float32
+        return int(_f32(_f32(1.15) * _f32(float(self._size))))
+
+    def Size(self) -> int:  # noqa: N802
+        return len(self._latest)
+
+    def SStableIterator(self):  # noqa: N802
+        return _Iterator(sorted(self._latest.items()))
+
+    def Flush(self, *writer_options):  # noqa: N802
+        """MemStore.Flush: keys whose latest op is a tombstone are left out."""
+        return self._flush(L.RIO_FLUSH_SKIP_TOMBSTONES, writer_options)
+
+    def FlushWithTombstones(self, *writer_options):  # noqa: N802
+        """MemStore.FlushWithTombstones: tombstoned keys are written with nil values."""
+        return self._flush(L.RIO_FLUSH_WITH_TOMBSTONES, writer_options)
+
+    def _op_key(self, op: int) -> bytes:
+        return bytes(self._keys[self._key_off[op]:self._key_off[op + 1]])
+
+    def _flush(self, mode, writer_options):
+        import numpy as np
+        import torch
+
+        from sstables import UnsupportedError, _WriterOpts
+        from sstables.merger import write_table_files
+
+        o = _WriterOpts()
+        for f in writer_options:
+            f(o)
+        if not o.basePath:
+            return GoError("basePath was not supplied")  # sstable_writer.go:232
+        if o.dataCompressionType not in (L.COMP_NONE, L.COMP_SNAPPY):
+            return UnsupportedError(f"output data compression {o.dataCompressionType}: the device encodes none and snappy")
+        if self._max_key_len > L.RIO_FLUSH_MAX_KEY_LEN:
+            return UnsupportedError(f"a key of {self._max_key_len} bytes: the device flush orders keys of up to "
+                                    f"{L.RIO_FLUSH_MAX_KEY_LEN}")
+        n = len(self._flags)
+        dev = f"cuda:{self.device}"
+        with torch.cuda.device(self.device):
+            up = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+            pad = bytearray(L.RIO_DEVICE_PAD)
+            keys = up(np.frombuffer(self._keys + pad, dtype=np.uint8))
+            values = up(np.frombuffer(self._values + pad, dtype=np.uint8))
+            key_off = up(np.asarray(self._key_off, dtype=np.int64))
+            val_off = up(np.asarray(self._val_off, dtype=np.int64))
+            flags = up(np.frombuffer(self._flags + bytearray(1), dtype=np.uint8))
+            view = L.OpsView(keys=keys.data_ptr(), key_off=key_off.data_ptr(), values=values.data_ptr(),
+                             val_off=val_off.data_ptr(), flags=flags.data_ptr(), n=n, key_bytes=len(self._keys),
+                             value_bytes=len(self._values))
+            c = flush_ops_on_device(L.default_ctx(self.device), self.device, view, mode, o.dataCompressionType,
+                                    max_key_len=self._max_key_len)
+            if c.status is not None:
+                return GoError(f"memstore flush '{o.basePath}': op {c.unsorted_table} of the log was rejected")
+            lo = hi = b""
+            if c.n_out:
+                first, last = (int(x) & _NONE for x in c.out_src[[0, c.n_out - 1]].cpu().tolist())
+                lo, hi = self._op_key(first), self._op_key(last)
+            write_table_files(o.basePath, c, lo, hi)
+        return None
+
+
+def NewMemStore(device: int = 0) -> MemStore:  # noqa: N802
+    return MemStore(device)

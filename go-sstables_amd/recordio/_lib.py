@@ -113,6 +113,25 @@ class SstView(ctypes.Structure):
     ]
 
 
+RIO_FLUSH_WITH_TOMBSTONES, RIO_FLUSH_SKIP_TOMBSTONES = 0, 1
+RIO_FLUSH_MAX_KEY_LEN = 1024
+
+
+class OpsView(ctypes.Structure):
+    """rio_ops_view (include/rio.h): a memstore's op log on the device."""
+
+    _fields_ = [
+        ("keys", c_void_p),
+        ("key_off", c_void_p),
+        ("values", c_void_p),
+        ("val_off", c_void_p),
+        ("flags", c_void_p),
+        ("n", c_uint64),
+        ("key_bytes", c_uint64),
+        ("value_bytes", c_uint64),
+    ]
+
+
 class IndexHit(ctypes.Structure):
     """rio_index_hit (include/rio.h)."""
 
@@ -240,6 +259,8 @@ _SIGS = {
     "rio_sst_index_encode": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p]),
     "rio_index_entry_len": (c_uint64, [c_uint64, c_uint64, c_uint64]),
     "rio_index_entries_bound": (c_uint64, [c_uint64, c_uint64]),
+    "rio_sst_flush_plan": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rio_sst_flush_stage_ms": (c_int, [c_void_p, POINTER(c_float), c_int]),
 }
 
 EXPORTED = tuple(_SIGS)

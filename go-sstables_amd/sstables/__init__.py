@@ -90,6 +90,24 @@ def ReadOnDevice(device: int):  # noqa: N802
     return f
 
 
+@dataclass
+class _WriterOpts:
+    basePath: str = ""
+    dataCompressionType: int = L.COMP_SNAPPY  # sstable_writer.go:219-220
+
+
+def WriteBasePath(p: str):  # noqa: N802
+    """sstable_writer.go:271 (a writer option of memstore.Flush / FlushWithTombstones)."""
+    def f(o): o.basePath = p
+    return f
+
+
+def DataCompressionType(c: int):  # noqa: N802
+    """sstable_writer.go:283; the device encodes recordio's none and snappy."""
+    def f(o): o.dataCompressionType = c
+    return f
+
+
 def _fmt_key(k: bytes) -> str:
     return "[" + " ".join(str(b) for b in k) + "]"  # Go's %v of a []byte
 

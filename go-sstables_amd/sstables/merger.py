@@ -68,39 +68,39 @@ class Compaction:
     out_src = data_img = data_len = index_img = index_len = None
 
 
-def compact_on_device(ctx, device: int, views, mode: int, comp: int, mark=None) -> Compaction:
-    """Plan, gather, data encode, index entries, index encode on torch's current stream. `views` is a
-    ctypes array of SstView. `mark(name)` is called after each stage is enqueued and after each of the two
-    host reads (benchmarks record an event there, so the host gaps are intervals of their own). The file images stay on the device; data_len / index_len are 1-element tensors."""
+def on_device_stream(device: int, fn):
+    """fn(stream handle) on torch's current stream of `device`; when that is the null stream, on a stream of
+    our own ordered after and before it (the null stream's handle would select the context's own stream,
+    which torch's copies do not follow)."""
     import torch
 
     cur = torch.cuda.current_stream(device)
     if cur.cuda_stream == 0:
-        # the null stream's handle would select the context's own stream, which torch's copies do not
-        # follow: run on a stream of our own, ordered after and before the caller's
         side = torch.cuda.Stream(device=device)
         side.wait_stream(cur)
         with torch.cuda.stream(side):
-            c = compact_on_device(ctx, device, views, mode, comp, mark)
+            out = fn(ctypes.c_void_p(side.cuda_stream))
         cur.wait_stream(side)
-        return c
+        return out
+    return fn(ctypes.c_void_p(cur.cuda_stream))
+
+
+def check_status(rc, what):
+    if rc:
+        raise GoError(f"{what}: {L.strerror(rc)}")
+
+
+def encode_planned(ctx, device: int, st, src, keep, res, comp: int, mark, refuse_dup: bool) -> Compaction:
+    """What follows a plan (rio_sst_merge_plan or rio_sst_flush_plan, whose view the context holds): result
+    read, gather, data encode, index entries, index encode, on stream `st`. src / keep / res are the plan's
+    outputs. Shared by compact_on_device and memstore.flush_ops_on_device."""
+    import torch
+
     lib = L.lib()
     dev = f"cuda:{device}"
-    st = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    mark = mark or (lambda name: None)
-    n_in = sum(v.n for v in views)
     i64 = lambda n: torch.empty(max(n, 1), dtype=torch.int64, device=dev)  # noqa: E731
     u8 = lambda n: torch.empty(max(n, 1), dtype=torch.uint8, device=dev)  # noqa: E731
-
-    def check(rc, what):
-        if rc:
-            raise GoError(f"{what}: {L.strerror(rc)}")
-
     c = Compaction()
-    src, keep, res = i64(n_in), u8(n_in), i64(L.RIO_MERGE_RESULT_WORDS)
-    check(lib.rio_sst_merge_plan(ctx, ctypes.addressof(views), len(views), mode, src.data_ptr(), keep.data_ptr(),
-                                 res.data_ptr(), st), "rio_sst_merge_plan")
-    mark("plan")
     # the one host round trip before the files are fetched: rio_device_encode takes n by value
     r = [x & _NONE for x in res.cpu().tolist()]
     mark("result_read")
@@ -109,35 +109,74 @@ def compact_on_device(ctx, device: int, views, mode: int, comp: int, mark=None) 
     if c.unsorted_table != _NONE:
         c.status = "unsorted"
         return c
-    if mode == L.RIO_MERGE_ALL and c.first_dup != _NONE:
+    if refuse_dup and c.first_dup != _NONE:
         c.status = "duplicate"
         return c
     n = c.n_out
     c.out_src, val_off, val_flags = i64(n), i64(n + 1), u8(n)
     values = u8(c.value_bytes + L.RIO_DEVICE_PAD)
-    check(lib.rio_sst_merge_gather(ctx, src.data_ptr(), keep.data_ptr(), n, c.out_src.data_ptr(), values.data_ptr(),
-                                   values.numel(), val_off.data_ptr(), val_flags.data_ptr(), st), "rio_sst_merge_gather")
+    check_status(lib.rio_sst_merge_gather(ctx, src.data_ptr(), keep.data_ptr(), n, c.out_src.data_ptr(), values.data_ptr(),
+                                    values.numel(), val_off.data_ptr(), val_flags.data_ptr(), st), "rio_sst_merge_gather")
     mark("gather")
     cap = int(lib.rio_encode_bound(n, c.value_bytes, comp))
     c.data_img, data_rec_off, c.data_len = u8(cap), i64(n), i64(1)
-    check(lib.rio_device_encode(ctx, values.data_ptr(), val_off.data_ptr(), val_flags.data_ptr(), n, c.value_bytes, comp,
-                                c.data_img.data_ptr(), cap, data_rec_off.data_ptr(), c.data_len.data_ptr(), st),
-          "rio_device_encode(data)")
+    check_status(lib.rio_device_encode(ctx, values.data_ptr(), val_off.data_ptr(), val_flags.data_ptr(), n, c.value_bytes, comp,
+                                 c.data_img.data_ptr(), cap, data_rec_off.data_ptr(), c.data_len.data_ptr(), st),
+           "rio_device_encode(data)")
     mark("data_encode")
     ecap = int(lib.rio_index_entries_bound(n, c.key_bytes)) + L.RIO_DEVICE_PAD
     entries, ent_off = u8(ecap), i64(n + 1)
-    check(lib.rio_sst_index_encode(ctx, c.out_src.data_ptr(), data_rec_off.data_ptr(), n, entries.data_ptr(),
-                                   ecap - L.RIO_DEVICE_PAD, ent_off.data_ptr(), st), "rio_sst_index_encode")
+    check_status(lib.rio_sst_index_encode(ctx, c.out_src.data_ptr(), data_rec_off.data_ptr(), n, entries.data_ptr(),
+                                    ecap - L.RIO_DEVICE_PAD, ent_off.data_ptr(), st), "rio_sst_index_encode")
     mark("index_entries")
     ent_bytes = int(ent_off[n].item())  # rio_device_encode sizes its scratch from the arena length
     mark("entries_length_read")
     icap = int(lib.rio_encode_bound(n, ent_bytes, L.COMP_NONE))
     c.index_img, index_rec_off, c.index_len = u8(icap), i64(n), i64(1)
-    check(lib.rio_device_encode(ctx, entries.data_ptr(), ent_off.data_ptr(), None, n, ent_bytes, L.COMP_NONE,
-                                c.index_img.data_ptr(), icap, index_rec_off.data_ptr(), c.index_len.data_ptr(), st),
-          "rio_device_encode(index)")
+    check_status(lib.rio_device_encode(ctx, entries.data_ptr(), ent_off.data_ptr(), None, n, ent_bytes, L.COMP_NONE,
+                                 c.index_img.data_ptr(), icap, index_rec_off.data_ptr(), c.index_len.data_ptr(), st),
+           "rio_device_encode(index)")
     mark("index_encode")
     return c
+
+
+def compact_on_device(ctx, device: int, views, mode: int, comp: int, mark=None) -> Compaction:
+    """Plan, gather, data encode, index entries, index encode on torch's current stream. `views` is a
+    ctypes array of SstView. `mark(name)` is called after each stage is enqueued and after each of the two
+    host reads (benchmarks record an event there, so the host gaps are intervals of their own). The file images stay on the device; data_len / index_len are 1-element tensors."""
+    import torch
+
+    mark = mark or (lambda name: None)
+    dev = f"cuda:{device}"
+    n_in = sum(v.n for v in views)
+
+    def run(st):
+        src = torch.empty(max(n_in, 1), dtype=torch.int64, device=dev)
+        keep = torch.empty(max(n_in, 1), dtype=torch.uint8, device=dev)
+        res = torch.empty(L.RIO_MERGE_RESULT_WORDS, dtype=torch.int64, device=dev)
+        check_status(L.lib().rio_sst_merge_plan(ctx, ctypes.addressof(views), len(views), mode, src.data_ptr(), keep.data_ptr(),
+                                          res.data_ptr(), st), "rio_sst_merge_plan")
+        mark("plan")
+        return encode_planned(ctx, device, st, src, keep, res, comp, mark, mode == L.RIO_MERGE_ALL)
+
+    return on_device_stream(device, run)
+
+
+def write_table_files(path: str, c: Compaction, min_key: bytes, max_key: bytes):
+    """data.rio, index.rio and meta.pb.bin of a finished Compaction (its images are fetched here)."""
+    from . import DataFileName, IndexFileName, MetaFileName
+
+    dn, ixn = int(c.data_len.item()), int(c.index_len.item())
+    data = bytes(c.data_img[:dn].cpu().numpy())
+    index = bytes(c.index_img[:ixn].cpu().numpy())
+    meta = proto.MetaData(version=1, numRecords=c.n_out, nullValues=c.null_values)
+    if c.n_out:
+        meta.minKey, meta.maxKey = min_key, max_key
+    meta.dataBytes, meta.indexBytes, meta.totalBytes = len(data), len(index), len(data) + len(index)
+    os.makedirs(path, exist_ok=True)
+    for name, b in ((DataFileName, data), (IndexFileName, index), (MetaFileName, meta.marshal())):
+        with open(os.path.join(path, name), "wb") as fh:
+            fh.write(b)
 
 
 class SSTableMerger:
@@ -164,7 +203,7 @@ class SSTableMerger:
     def _run(self, readers, path, mode, comp):
         import torch
 
-        from . import DataFileName, IndexFileName, MetaFileName, SSTableReader, UnsupportedError
+        from . import SSTableReader, UnsupportedError
 
         comp = self.data_compression if comp is None else comp
         if comp not in (L.COMP_NONE, L.COMP_SNAPPY):
@@ -198,19 +237,12 @@ class SSTableMerger:
                                         "ascending")
             if c.status == "duplicate":
                 return GoError(f"sstables.WriteNext '{path}': the same key cannot be written more than once")
-            dn, ixn = int(c.data_len.item()), int(c.index_len.item())
-            data = bytes(c.data_img[:dn].cpu().numpy())
-            index = bytes(c.index_img[:ixn].cpu().numpy())
-            meta = proto.MetaData(version=1, numRecords=c.n_out, nullValues=c.null_values)
+            lo = hi = b""
             if c.n_out:
                 first, last = (int(x) & _NONE for x in c.out_src[[0, c.n_out - 1]].cpu().tolist())
-                meta.minKey = readers[first >> L.RIO_MERGE_ENTRY_BITS].t.key(first & _ENTRY_MASK)
-                meta.maxKey = readers[last >> L.RIO_MERGE_ENTRY_BITS].t.key(last & _ENTRY_MASK)
-        meta.dataBytes, meta.indexBytes, meta.totalBytes = len(data), len(index), len(data) + len(index)
-        os.makedirs(path, exist_ok=True)
-        for name, b in ((DataFileName, data), (IndexFileName, index), (MetaFileName, meta.marshal())):
-            with open(os.path.join(path, name), "wb") as fh:
-                fh.write(b)
+                lo = readers[first >> L.RIO_MERGE_ENTRY_BITS].t.key(first & _ENTRY_MASK)
+                hi = readers[last >> L.RIO_MERGE_ENTRY_BITS].t.key(last & _ENTRY_MASK)
+            write_table_files(path, c, lo, hi)
         return None
 
 

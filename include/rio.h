@@ -377,7 +377,8 @@ typedef struct rio_sst_view {
 #define RIO_MERGE_R_UNSORTED 4u     /* first table whose keys are not strictly ascending, or whose key / value
                                        ranges leave their arenas; ~0 = none. Nothing else of the plan is
                                        meaningful then (the caller returns RIO_ERR_UNSUPPORTED): merged
-                                       positions can collide, so d_src and d_keep may be partly unwritten */
+                                       positions can collide, so d_src and d_keep may be partly unwritten.
+                                       rio_sst_flush_plan reuses the word for the first rejected OP */
 #define RIO_MERGE_R_KEY_BYTES 5u    /* key bytes of the survivors (sizes rio_sst_index_encode's output) */
 /* Plan: order all N = sum of views[t].n entries by (key, table position) and decide survival.
  *   d_src  [N] entry at merged position p = views[d_src[p] >> 40] entry (d_src[p] & (2^40 - 1))
@@ -411,6 +412,57 @@ int rio_sst_index_encode(rio_ctx* ctx, const uint64_t* d_out_src, const uint64_t
 /* host helpers: the marshalled length of one IndexEntry, and the arena bound for n of them */
 uint64_t rio_index_entry_len(uint64_t key_len, uint64_t value_offset, uint64_t checksum);
 uint64_t rio_index_entries_bound(uint64_t n, uint64_t key_bytes);
+
+/* ---- memstore flush on the device (rio_flush.hip) ---------------------------------------------
+ * Replaces MemStore.Flush / FlushWithTombstones (memstore/memstore.go:189-238: a walk over the skip
+ * list, one WriteNext per key) for a memstore kept as an append-only log of operations in
+ * application order. Op i = key keys[key_off[i] .. key_off[i + 1]) with value
+ * values[val_off[i] .. val_off[i + 1]); flags[i] & RIO_FLAG_NIL marks a tombstone (Delete /
+ * Tombstone: the value is nil, its range is not read). Op i is applied after op i - 1, so the last
+ * op of a key is the key's state. The key arena has RIO_DEVICE_PAD readable bytes past key_bytes
+ * (the contract of rio_device_encode's records). */
+typedef struct rio_ops_view {
+    const uint8_t* keys;       /* key arena */
+    const uint64_t* key_off;   /* [n + 1] */
+    const uint8_t* values;     /* value arena */
+    const uint64_t* val_off;   /* [n + 1] */
+    const uint8_t* flags;      /* [n] RIO_FLAG_NIL marks a tombstone */
+    uint64_t n;                /* ops */
+    uint64_t key_bytes;        /* length of the key arena: keys are clamped to it */
+    uint64_t value_bytes;      /* length of the value arena: values are clamped to it */
+} rio_ops_view;
+#define RIO_FLUSH_WITH_TOMBSTONES 0u /* FlushWithTombstones: latest op of every key, nil values too */
+#define RIO_FLUSH_SKIP_TOMBSTONES 1u /* Flush: keys whose latest op is nil are left out */
+#define RIO_FLUSH_MAX_KEY_LEN 1024u
+/* Plan of a flush: order the n ops by (key, op index) with the bytes comparator (lexicographic,
+ * unsigned, a proper prefix first) and keep the last op of every key; under
+ * RIO_FLUSH_SKIP_TOMBSTONES a key whose last op is nil is dropped, an empty non-nil value is kept
+ * (memstore.go:229).
+ *   d_src  [n] op at sorted position p (table bits 0: the word rio_sst_merge_gather takes)
+ *   d_keep [n] 1 when position p goes to the table
+ *   d_result   the block of rio_sst_merge_plan: RIO_MERGE_R_N_OUT, _VALUE_BYTES, _NULL_VALUES and
+ *              _KEY_BYTES as for a merge; RIO_MERGE_R_FIRST_DUP is always ~0; RIO_MERGE_R_UNSORTED
+ *              holds the first OP (not table) whose key or value range is not monotone, leaves its
+ *              arena, or whose key is longer than max_key_len; ~0 = none. Nothing else of the plan is
+ *              meaningful then.
+ * The plan registers ONE rio_sst_view on the context as the last plan (keys = the index arena, values
+ * = the data arena, key lengths and the CRC-64 of every kept value in context scratch), so
+ * rio_sst_merge_gather and rio_sst_index_encode follow it exactly as they follow rio_sst_merge_plan;
+ * the op arrays must stay valid until those calls have run. The ordering is an LSD radix sort over
+ * the key length and the ceil(max_key_len / 8) big-endian 8-byte chunks of the keys: max_key_len is
+ * a bound on the key lengths, it sets the pass count (pass the longest key's length, 0 .. RIO_FLUSH_MAX_KEY_LEN).
+ * Scratch (40 bytes per op, the sort's temp and the gather's 16 bytes per op) is sized here, nothing is allocated afterwards.
+ * Stream-ordered (NULL = the ctx stream), never waits for the stream (only for the previous plan's
+ * copy of its view, as rio_sst_merge_plan). Every index read back from a buffer is clamped: a wrong
+ * input gives RIO_MERGE_R_UNSORTED or wrong bytes, never an out-of-range access.
+ * Returns RIO_ERR_ARG for a NULL ctx / ops / d_result, an unknown mode or n > 0 with a NULL array,
+ * RIO_ERR_UNSUPPORTED for n >= 2^31 - 1 or max_key_len > RIO_FLUSH_MAX_KEY_LEN, before any device call. */
+int rio_sst_flush_plan(rio_ctx* ctx, const rio_ops_view* ops, uint32_t mode, uint32_t max_key_len, uint64_t* d_src,
+                       uint8_t* d_keep, uint64_t* d_result, void* stream);
+/* Stage milliseconds of the context's last flush plan, recorded while rio_ctx_set_timing is on: check,
+ * the length pass, the chunk passes (last chunk first), keep, crc. Fills up to n entries and returns
+ * the count (0 when timing is off or the log was empty). Waits for the plan's last stage. */
+int rio_sst_flush_stage_ms(rio_ctx* ctx, float* ms, int n);
 
 /* ---- DiskKeyIndex lookups (sstables/disk_key_index.go:87-140) --------------------------------
  * Batched DiskKeyIndex.Get / Contains / IteratorStartingAt: one result per query key, each the
