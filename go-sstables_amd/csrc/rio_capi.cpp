@@ -63,6 +63,9 @@ hipError_t launch_merge_gather(const GatherParams& P, void* cub_tmp, size_t cub_
 hipError_t launch_index_entries(const EntryParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
 size_t flush_cub_bytes(uint64_t n, uint32_t max_key_len);
 hipError_t launch_flush_plan(const FlushParams& P, hipStream_t s, hipEvent_t* ev, uint32_t* n_stages);
+size_t wal_cub_bytes(uint64_t n);
+hipError_t launch_wal_plan(const WalParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
+hipError_t launch_wal_gather(const WalParams& P, hipStream_t s);
 hipError_t launch_read_at(const uint8_t* f, uint64_t len, uint64_t off, uint8_t* out, uint64_t out_cap,
                           ReadAtResult* res, hipStream_t s);
 int build_seek_map(const uint8_t* f, uint64_t len, const uint64_t* rec_off, const uint8_t* flags, uint64_t n,
@@ -238,6 +241,13 @@ struct rio_ctx {
     DevBuf fl_len, fl_crc, fl_dig, fl_perm, fl_cub;
     std::vector<hipEvent_t> fl_ev;
     uint32_t fl_stages = 0;
+    // rio_wal_ops_plan: the last plan's segments + record bases (device and host copies), the per-record scratch
+    // (WalParams, one allocation), scan temp; wal_P holds the scratch pointers for the gather
+    DevBuf wal_segs, wal_scr, wal_cub;
+    std::vector<uint64_t> wal_host;
+    WalParams wal_P{};
+    bool wal_planned = false;
+    hipEvent_t wal_ev = nullptr;  // recorded after the last plan's copy of wal_host
     uint8_t* pinned[2] = {nullptr, nullptr};
     hipEvent_t pin_ev[2] = {};
     // device-API calls share the ctx's scratch: a call on another stream than the previous one waits
@@ -429,6 +439,10 @@ extern "C" void rio_ctx_destroy(rio_ctx* c) {
         hipEventSynchronize(c->mrg_ev);
         hipEventDestroy(c->mrg_ev);
     }
+    if (c->wal_ev) {  // the last plan's segment copy reads wal_host
+        hipEventSynchronize(c->wal_ev);
+        hipEventDestroy(c->wal_ev);
+    }
     c->fa.release();
     for (auto& a : c->batch) a->release();
     for (DevBuf* b : {&c->sink, &c->file, &c->out, &c->out_off, &c->rec_off, &c->flags,
@@ -436,7 +450,7 @@ extern "C" void rio_ctx_destroy(rio_ctx* c) {
                       &c->enc_hdr, &c->enc_size, &c->enc_tmp, &c->enc_cub, &c->enc_rec, &c->enc_rec_off, &c->enc_flags, &c->enc_out,
                       &c->enc_out_off, &c->enc_len, &c->q_pfx, &c->q_pfx_out, &c->q_idx, &c->q_perm, &c->q_tmp,
                       &c->mrg_views, &c->mrg_pfx, &c->mrg_tmp, &c->mrg_opos, &c->mrg_cub, &c->fl_len, &c->fl_crc, &c->fl_dig,
-                      &c->fl_perm, &c->fl_cub})
+                      &c->fl_perm, &c->fl_cub, &c->wal_segs, &c->wal_scr, &c->wal_cub})
         b->release();
     for (hipEvent_t e : c->fl_ev) hipEventDestroy(e);
     for (int i = 0; i < 2; i++) {
@@ -1792,6 +1806,90 @@ extern "C" int rio_sst_flush_stage_ms(rio_ctx* ctx, float* ms, int n) {
     for (uint32_t i = 0; i < k; i++)
         if (hipEventElapsedTime(&ms[i], ctx->fl_ev[i], ctx->fl_ev[i + 1]) != hipSuccess) return 0;
     return (int)k;
+}
+
+// ------------------------------------------------------------------------------------------
+// WAL recovery: WalMutation records of decoded WAL files to an op log (rio_walops.hip)
+// ------------------------------------------------------------------------------------------
+// As for the merge entry points: every argument check stands before the first read of *ctx
+// (tests/test_wal_mutation_host.py calls both with a placeholder ctx on a machine without a GPU).
+extern "C" int rio_wal_ops_plan(rio_ctx* ctx, const rio_wal_segment* segs, uint32_t n_segs, uint64_t* d_result,
+                                void* stream) {
+    if (!ctx || !segs || !d_result || n_segs == 0) return RIO_ERR_ARG;
+    if (n_segs > RIO_WAL_MAX_SEGMENTS) return RIO_ERR_UNSUPPORTED;
+    static_assert(sizeof(rio_wal_segment) % 8 == 0, "segments and bases share one uint64 buffer");
+    const size_t sw = sizeof(rio_wal_segment) / 8 * n_segs;
+    std::vector<uint64_t> host(sw + n_segs + 1);
+    memcpy(host.data(), segs, sw * 8);
+    uint64_t N = 0;
+    for (uint32_t t = 0; t < n_segs; t++) {
+        const rio_wal_segment& g = segs[t];
+        if (g.n && (!g.out || !g.out_off || !g.flags)) return RIO_ERR_ARG;
+        if (g.n >= (1ull << 31) - 1) return RIO_ERR_UNSUPPORTED;
+        host[sw + t] = N;
+        N += g.n;
+        if (N >= (1ull << 31) - 1) return RIO_ERR_UNSUPPORTED;
+    }
+    host[sw + n_segs] = N;
+    // from here on *ctx is read
+    HIP_TRY(hipSetDevice(ctx->device));
+    ctx->wal_planned = false;
+    // the scratch of both calls, sized here and nowhere later: 8 uint64 arrays of N + 1, the two meta words, and
+    // a 32-bit word per record (kind and segment)
+    const size_t words = 8 * (N + 1) + 2;
+    HIP_TRY(ctx->wal_segs.ensure(host.size() * 8));
+    HIP_TRY(ctx->wal_scr.ensure(words * 8 + 4 * (N + 1)));
+    HIP_TRY(ctx->wal_cub.ensure(std::max<size_t>(wal_cub_bytes(N), 256)));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    // as rio_sst_merge_plan: the host copy lives in the context until the next plan, which waits for this
+    // plan's copy of it, not for the stream
+    if (!ctx->wal_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->wal_ev, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(ctx->wal_ev));
+    ctx->wal_host.swap(host);
+    HIP_TRY(hipMemcpyAsync(ctx->wal_segs.p, ctx->wal_host.data(), ctx->wal_host.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(ctx->wal_ev, s));
+    WalParams P{};
+    P.segs = ctx->wal_segs.as<rio_wal_segment>();
+    P.base = ctx->wal_segs.as<uint64_t>() + sw;
+    P.S = n_segs;
+    P.N = N;
+    uint64_t* w = ctx->wal_scr.as<uint64_t>();
+    uint64_t** arrays[8] = {&P.koff, &P.voff, &P.klen, &P.vlen, &P.isop, &P.opos, &P.kdst, &P.vdst};
+    for (uint64_t** a : arrays) {
+        *a = w;
+        w += N + 1;
+    }
+    P.meta = w;
+    P.rec = reinterpret_cast<uint32_t*>(w + 2);
+    P.result = d_result;
+    HIP_TRY(launch_wal_plan(P, ctx->wal_cub.p, ctx->wal_cub.cap, s));
+    ctx->wal_P = P;
+    ctx->wal_planned = true;
+    return RIO_OK;
+}
+
+extern "C" int rio_wal_ops_gather(rio_ctx* ctx, uint64_t n_ops, uint8_t* d_keys, uint64_t keys_cap, uint64_t* d_key_off,
+                                  uint8_t* d_values, uint64_t values_cap, uint64_t* d_val_off, uint8_t* d_flags,
+                                  uint64_t* d_op_rec, void* stream) {
+    if (!ctx || !d_key_off || !d_val_off || (n_ops && (!d_keys || !d_values || !d_flags))) return RIO_ERR_ARG;
+    // from here on *ctx is read
+    if (!ctx->wal_planned) return RIO_ERR_STATE;
+    if (n_ops > ctx->wal_P.N) return RIO_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    WalParams P = ctx->wal_P;
+    P.result = nullptr;
+    P.n_ops = n_ops;
+    P.keys = d_keys;
+    P.keys_cap = keys_cap;
+    P.key_off = d_key_off;
+    P.values = d_values;
+    P.values_cap = values_cap;
+    P.val_off = d_val_off;
+    P.flags = d_flags;
+    P.op_rec = d_op_rec;
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    HIP_TRY(launch_wal_gather(P, s));
+    return RIO_OK;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -239,6 +239,37 @@ struct FlushParams {
 };
 constexpr uint32_t kFlushMaxStages = (RIO_FLUSH_MAX_KEY_LEN + 7) / 8 + 1 + 3;  // check, passes, keep, crc
 
+// rio_walops.hip: WalMutation records of decoded WAL files to an op log (rio_wal_ops_plan / _gather)
+constexpr uint8_t kWalNoOp = 0, kWalUpsert = 1, kWalTombstone = 2;
+struct WalParams {
+    const rio_wal_segment* segs;  // [S] device copy of the caller's segments
+    const uint64_t* base;         // [S + 1] number of segment s's first record among all N records
+    uint32_t S;
+    uint64_t N;
+    // per record, written by the plan (context scratch)
+    uint32_t* rec;                // [N] kWal* | segment << 8
+    uint64_t* koff;               // [N] key range in the segment's arena (offset; the length is klen)
+    uint64_t* voff;               // [N] value range
+    uint64_t* klen;               // [N + 1] scan inputs: 0 for a record without an op
+    uint64_t* vlen;               // [N + 1]
+    uint64_t* isop;               // [N + 1]
+    uint64_t* opos;               // [N + 1] exclusive scans: op number, key and value arena offsets
+    uint64_t* kdst;               // [N + 1]
+    uint64_t* vdst;               // [N + 1]
+    uint64_t* meta;               // [2] smallest (bad record << 3 | class), longest key
+    uint64_t* result;             // [RIO_WAL_RESULT_WORDS]
+    // the gather's outputs
+    uint64_t n_ops;
+    uint8_t* keys;
+    uint64_t keys_cap;
+    uint64_t* key_off;            // [n_ops + 1]
+    uint8_t* values;
+    uint64_t values_cap;
+    uint64_t* val_off;            // [n_ops + 1]
+    uint8_t* flags;               // [n_ops]
+    uint64_t* op_rec;             // [n_ops] or null
+};
+
 // protobuf varint length, and proto.Marshal's size of an IndexEntry {key = 1, valueOffset = 2, checksum = 3}:
 // proto3 omits an empty key and zero scalars (sstables/proto/sstable.proto:5-9)
 #ifdef __HIPCC__

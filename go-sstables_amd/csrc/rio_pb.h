@@ -156,6 +156,109 @@ __device__ __forceinline__ bool pb_data_entry_t(B& g, uint64_t base, uint64_t le
     return true;
 }
 
+// Go's utf8.Valid over bytes [off, off + len) of a source: shortest forms only, no surrogates
+// (D800-DFFF), nothing above U+10FFFF, no stray or missing continuation bytes
+template <class B>
+__device__ __forceinline__ bool pb_utf8_valid_t(B& g, uint64_t base, uint64_t off, uint64_t len) {
+    uint64_t p = off;
+    const uint64_t end = off + len;
+    while (p < end) {
+        const uint32_t c = g(base + p++);
+        if (c < 0x80) continue;
+        uint32_t more, lo = 0x80, hi = 0xBF;  // continuation count, bounds of the first continuation
+        if (c >= 0xC2 && c <= 0xDF) {
+            more = 1;
+        } else if (c >= 0xE0 && c <= 0xEF) {
+            more = 2;
+            if (c == 0xE0) lo = 0xA0;
+            if (c == 0xED) hi = 0x9F;
+        } else if (c >= 0xF0 && c <= 0xF4) {
+            more = 3;
+            if (c == 0xF0) lo = 0x90;
+            if (c == 0xF4) hi = 0x8F;
+        } else {
+            return false;  // 80..C1, F5..FF
+        }
+        if (end - p < more) return false;
+        for (uint32_t k = 0; k < more; k++) {
+            const uint32_t x = g(base + p++);
+            if (x < lo || x > hi) return false;
+            lo = 0x80;
+            hi = 0xBF;
+        }
+    }
+    return true;
+}
+
+// proto.Unmarshal into a reset WalMutation (simpledb/proto/wal_mutation.pb.go:26-29, 94-95, 215-219):
+//   oneof mutation { UpsertMutation addition = 1; DeleteTombstoneMutation deleteTombStone = 2; }
+//   UpsertMutation          { string key = 1; string value = 2; bytes keyBytes = 3; bytes valueBytes = 4; }
+//   DeleteTombstoneMutation { string key = 1; bytes keyBytes = 2; }
+// Fields in wire order; the member seen last is the oneof's. A member seen again while it is the current one
+// merges (every field keeps its last occurrence); the other member starts empty. A known field with another
+// wire type and every other field number are skipped, at both levels. Every occurrence of a string field must
+// be valid UTF-8, a replaced one too. Ranges are relative to base; an absent field has length 0.
+constexpr uint32_t kPbWalOk = 0, kPbWalBadProto = 1, kPbWalBadUtf8 = 2;
+struct PbWalMutation {
+    uint32_t member;  // 0 none, 1 addition, 2 deleteTombStone
+    uint64_t key_off, key_len;  // string key
+    uint64_t val_off, val_len;  // string value (addition)
+    uint64_t kb_off, kb_len;    // keyBytes
+    uint64_t vb_off, vb_len;    // valueBytes (addition)
+};
+template <class B>
+__device__ __forceinline__ uint32_t pb_wal_mutation_t(B& g, uint64_t base, uint64_t len, PbWalMutation& m) {
+    uint64_t pos = 0;
+    m = PbWalMutation{};
+    while (pos < len) {
+        uint64_t tag, v;
+        if (!pb_varint_t(g, base, len, pos, tag)) return kPbWalBadProto;
+        const uint64_t fn = tag >> 3;
+        const uint32_t wt = (uint32_t)(tag & 7);
+        if (fn < 1 || fn > 0x1FFFFFFFull) return kPbWalBadProto;
+        if (!((fn == 1 || fn == 2) && wt == 2)) {
+            if (!pb_skip_t(g, base, len, pos, fn, wt)) return kPbWalBadProto;
+            continue;
+        }
+        if (!pb_varint_t(g, base, len, pos, v) || v > len - pos) return kPbWalBadProto;
+        if (m.member != (uint32_t)fn) {
+            m = PbWalMutation{};
+            m.member = (uint32_t)fn;
+        }
+        const uint64_t end = pos + v;
+        const uint64_t kb_field = fn == 1 ? 3 : 2;  // keyBytes' number in this member
+        while (pos < end) {
+            uint64_t t2, l2;
+            if (!pb_varint_t(g, base, end, pos, t2)) return kPbWalBadProto;
+            const uint64_t f2 = t2 >> 3;
+            const uint32_t w2 = (uint32_t)(t2 & 7);
+            if (f2 < 1 || f2 > 0x1FFFFFFFull) return kPbWalBadProto;
+            const bool is_key = f2 == 1, is_val = fn == 1 && f2 == 2, is_kb = f2 == kb_field, is_vb = fn == 1 && f2 == 4;
+            if (w2 != 2 || !(is_key || is_val || is_kb || is_vb)) {
+                if (!pb_skip_t(g, base, end, pos, f2, w2)) return kPbWalBadProto;
+                continue;
+            }
+            if (!pb_varint_t(g, base, end, pos, l2) || l2 > end - pos) return kPbWalBadProto;
+            if ((is_key || is_val) && !pb_utf8_valid_t(g, base, pos, l2)) return kPbWalBadUtf8;
+            if (is_key) {
+                m.key_off = pos;
+                m.key_len = l2;
+            } else if (is_val) {
+                m.val_off = pos;
+                m.val_len = l2;
+            } else if (is_kb) {
+                m.kb_off = pos;
+                m.kb_len = l2;
+            } else {
+                m.vb_off = pos;
+                m.vb_len = l2;
+            }
+            pos += l2;
+        }
+    }
+    return kPbWalOk;
+}
+
 // pointer forms (b[0, n))
 __device__ __forceinline__ bool pb_varint(const uint8_t* b, uint64_t n, uint64_t& pos, uint64_t& v) {
     RawBytes g{b};

@@ -132,6 +132,25 @@ class OpsView(ctypes.Structure):
     ]
 
 
+RIO_WAL_MAX_SEGMENTS = 4096
+RIO_WAL_RESULT_WORDS = 8
+(RIO_WAL_R_N_RECORDS, RIO_WAL_R_N_OPS, RIO_WAL_R_KEY_BYTES, RIO_WAL_R_VALUE_BYTES, RIO_WAL_R_MAX_KEY_LEN,
+ RIO_WAL_R_FIRST_BAD, RIO_WAL_R_BAD_CLASS) = range(7)
+RIO_WAL_BAD_PROTO, RIO_WAL_BAD_UTF8, RIO_WAL_BAD_VALUE_NIL, RIO_WAL_BAD_RANGE = 1, 2, 3, 4
+
+
+class WalSegment(ctypes.Structure):
+    """rio_wal_segment (include/rio.h): one decoded WAL file on the device."""
+
+    _fields_ = [
+        ("out", c_void_p),
+        ("out_off", c_void_p),
+        ("flags", c_void_p),
+        ("n", c_uint64),
+        ("out_bytes", c_uint64),
+    ]
+
+
 class IndexHit(ctypes.Structure):
     """rio_index_hit (include/rio.h)."""
 
@@ -261,6 +280,10 @@ _SIGS = {
     "rio_index_entries_bound": (c_uint64, [c_uint64, c_uint64]),
     "rio_sst_flush_plan": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rio_sst_flush_stage_ms": (c_int, [c_void_p, POINTER(c_float), c_int]),
+    "rio_wal_ops_plan": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),
+    "rio_wal_ops_gather": (
+        c_int, [c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p,
+                c_void_p]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -464,6 +464,71 @@ int rio_sst_flush_plan(rio_ctx* ctx, const rio_ops_view* ops, uint32_t mode, uin
  * the count (0 when timing is off or the log was empty). Waits for the plan's last stage. */
 int rio_sst_flush_stage_ms(rio_ctx* ctx, float* ms, int n);
 
+/* ---- WAL recovery on the device: WalMutation records to an op log (rio_walops.hip) -------------
+ * Replaces the host loop of simpledb's replayAndSetupWriteAheadLog (simpledb/recovery.go:208-240):
+ * proto.Unmarshal of every WAL record into a WalMutation (simpledb/proto/wal_mutation.pb.go), then
+ * memStore.Upsert / Tombstone. Input: the decoded WAL files as rio_device_decode leaves them in HBM,
+ * one rio_wal_segment per file in replay order; output: a rio_ops_view for rio_sst_flush_plan
+ * (FlushWithTombstones, flush.go). Nothing is copied to the host but the plan's result block.
+ *
+ * Record rules (proto.Unmarshal into a reset message + the switch at recovery.go:224-237):
+ * WalMutation is oneof { addition = 1 (UpsertMutation: 1 key string, 2 value string, 3 keyBytes,
+ * 4 valueBytes); deleteTombStone = 2 (DeleteTombstoneMutation: 1 key string, 2 keyBytes) }, all wire
+ * type 2. Fields in wire order; the member seen last is the oneof's; a member seen again while current
+ * merges field by field (last occurrence wins), a switch to the other member starts it empty. A known
+ * field with another wire type and unknown fields are skipped at both levels. Every occurrence of a
+ * string field must be valid UTF-8 (Go's utf8.Valid). No member (a nil or empty record too): no op, the
+ * record still counts. addition: (keyBytes, valueBytes) when keyBytes is non-empty, with an absent or
+ * empty valueBytes refused as Upsert(key, nil); otherwise (key, value) as bytes, both may be empty.
+ * deleteTombStone: a tombstone of keyBytes when non-empty, otherwise of key. */
+typedef struct rio_wal_segment {      /* one decoded WAL file, in replay order */
+    const uint8_t* out;               /* rio_device_decode's d_out; RIO_DEVICE_PAD readable bytes past out_bytes */
+    const uint64_t* out_off;          /* [n + 1] */
+    const uint8_t* flags;             /* [n]; RIO_FLAG_NIL = nil record (Unmarshal of nil: the empty mutation) */
+    uint64_t n;                       /* records to replay (the caller has already cut at first_bad / its read error) */
+    uint64_t out_bytes;               /* arena length: every range is clamped to it */
+} rio_wal_segment;
+#define RIO_WAL_MAX_SEGMENTS 4096u
+/* d_result of rio_wal_ops_plan (uint64[RIO_WAL_RESULT_WORDS]) */
+#define RIO_WAL_RESULT_WORDS 8u
+#define RIO_WAL_R_N_RECORDS 0u    /* recovery.go's numRecords: every record, no-ops too */
+#define RIO_WAL_R_N_OPS 1u        /* upserts + tombstones */
+#define RIO_WAL_R_KEY_BYTES 2u    /* key arena length */
+#define RIO_WAL_R_VALUE_BYTES 3u  /* value arena length */
+#define RIO_WAL_R_MAX_KEY_LEN 4u  /* the longest key: what rio_sst_flush_plan takes as max_key_len */
+#define RIO_WAL_R_FIRST_BAD 5u    /* first refused record, counted over all segments; ~0 = none. When set,
+                                     nothing else in the block is meaningful: the reference fails recovery
+                                     at that record and flushes nothing */
+#define RIO_WAL_R_BAD_CLASS 6u    /* RIO_WAL_BAD_* of that record */
+#define RIO_WAL_BAD_PROTO 1u      /* proto.Unmarshal fails: malformed wire data at either message level */
+#define RIO_WAL_BAD_UTF8 2u       /* a proto3 string field (key / value) is not valid UTF-8 */
+#define RIO_WAL_BAD_VALUE_NIL 3u  /* Upsert(key, nil): memstore.ValueNil (memstore.go:124) */
+#define RIO_WAL_BAD_RANGE 4u      /* the segment's offsets are not monotone or leave its arena */
+/* Plan: copy the segments to the context (as rio_sst_merge_plan copies its views: only the previous
+ * plan's copy is waited for, so the plan is not graph-capturable), size the context's scratch for both
+ * calls (68 bytes per record plus the scan's temp), parse every record (one lane per record over the
+ * concatenation of the segments) and scan the op flags and the key and value lengths. The caller reads
+ * d_result (64 bytes), the sequence's one host round trip, and sizes the gather's outputs from it. Of
+ * several refused records the smallest index is reported. Every offset read from a buffer is clamped to
+ * its arena: a wrong input gives RIO_WAL_BAD_RANGE or wrong bytes, never an out-of-range access.
+ * Returns RIO_ERR_ARG for a NULL ctx / segs / d_result, n_segs = 0 or a segment with n > 0 and a NULL
+ * array, RIO_ERR_UNSUPPORTED for n_segs > RIO_WAL_MAX_SEGMENTS or 2^31 - 1 records and more, before any
+ * device call. Stream-ordered (NULL = the ctx stream). */
+int rio_wal_ops_plan(rio_ctx* ctx, const rio_wal_segment* segs, uint32_t n_segs, uint64_t* d_result, void* stream);
+/* Gather of the last plan's ops (n_ops = d_result[RIO_WAL_R_N_OPS]) into the arrays of a rio_ops_view:
+ *   d_keys    [keys_cap]    keys back to back; keys_cap >= key bytes (+ RIO_DEVICE_PAD for the flush)
+ *   d_key_off [n_ops + 1]
+ *   d_values  [values_cap]  values back to back; a tombstone has none
+ *   d_val_off [n_ops + 1]
+ *   d_flags   [n_ops]       RIO_FLAG_NIL for a tombstone
+ *   d_op_rec  [n_ops]       source record of each op, counted over all segments (may be NULL)
+ * A key or value that would pass its cap is not copied. Allocates nothing; the segments' arrays must
+ * still be valid. RIO_ERR_STATE without a plan on this context, RIO_ERR_ARG for a NULL ctx or output or
+ * n_ops larger than the plan's record count. Stream-ordered (NULL = the ctx stream). */
+int rio_wal_ops_gather(rio_ctx* ctx, uint64_t n_ops, uint8_t* d_keys, uint64_t keys_cap, uint64_t* d_key_off,
+                       uint8_t* d_values, uint64_t values_cap, uint64_t* d_val_off, uint8_t* d_flags,
+                       uint64_t* d_op_rec /* may be NULL: source record index of each op */, void* stream);
+
 /* ---- DiskKeyIndex lookups (sstables/disk_key_index.go:87-140) --------------------------------
  * Batched DiskKeyIndex.Get / Contains / IteratorStartingAt: one result per query key, each the
  * reference's binarySearch over the byte offsets of an uncompressed index.rio with every probe
