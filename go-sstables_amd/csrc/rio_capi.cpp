@@ -14,6 +14,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cmath>
 #include <array>
 #include <atomic>
 #include <memory>
@@ -61,6 +62,11 @@ size_t merge_cub_bytes(uint64_t n);
 hipError_t launch_merge_plan(const MergeParams& P, hipStream_t s);
 hipError_t launch_merge_gather(const GatherParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
 hipError_t launch_index_entries(const EntryParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
+// rio_bloom.hip
+hipError_t launch_bloom_add(const BloomParams& P, bool survivors, hipStream_t s);
+hipError_t launch_bloom_contains(const BloomParams& P, hipStream_t s);
+hipError_t launch_sst_key_prefixes(const rio_sst_view& v, uint64_t* pfx, hipStream_t s);
+hipError_t launch_sst_lookup(const BloomParams& P, const LookupParams& Q, hipStream_t s);
 size_t flush_cub_bytes(uint64_t n, uint32_t max_key_len);
 hipError_t launch_flush_plan(const FlushParams& P, hipStream_t s, hipEvent_t* ev, uint32_t* n_stages);
 size_t wal_cub_bytes(uint64_t n);
@@ -1712,6 +1718,114 @@ extern "C" int rio_sst_index_encode(rio_ctx* ctx, const uint64_t* d_out_src, con
     P.ent_off = d_ent_off;
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
     HIP_TRY(launch_index_entries(P, ctx->mrg_cub.p, ctx->mrg_cub.cap, s));
+    return RIO_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// bloom filters and point lookups of a loaded table (rio_bloom.hip)
+// ------------------------------------------------------------------------------------------
+// bloomfilter.NewOptimal (OptimalM / OptimalK): sstable_writer.go:79 sizes every table's filter with it
+extern "C" int rio_bloom_optimal(uint64_t max_n, double p, uint64_t* m, uint64_t* k) {
+    if (!m || !k || max_n == 0 || !(p > 0.0 && p < 1.0)) return RIO_ERR_ARG;
+    const double ln2 = 0.693147180559945309417232121458176568;  // Go's math.Ln2
+    const double dm = std::ceil(-(double)max_n * std::log(p) / (ln2 * ln2));
+    if (!(dm < 18446744073709551616.0)) return RIO_ERR_ARG;
+    *m = (uint64_t)dm;
+    *k = (uint64_t)std::ceil(ln2 * (double)*m / (double)max_n);
+    return RIO_OK;
+}
+
+// As for the merge entry points: every argument check stands before the first read of *ctx
+// (tests/test_bloom_host.py calls these with a placeholder ctx on a machine without a GPU).
+static bool bloom_view_ok(const rio_bloom_view* f) {
+    return f && f->k >= 1 && f->k <= RIO_BLOOM_MAX_K && f->m >= 2;
+}
+
+extern "C" int rio_bloom_add(rio_ctx* ctx, const rio_bloom_view* f, const uint8_t* d_keys, const uint64_t* d_key_off,
+                             uint64_t n, uint64_t key_bytes, void* stream) {
+    if (!ctx || !bloom_view_ok(f)) return RIO_ERR_ARG;
+    if (n == 0) return RIO_OK;
+    if (!f->bits || !f->hash_keys || !d_keys || !d_key_off) return RIO_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    BloomParams P{};
+    P.f = *f;
+    P.keys = d_keys;
+    P.key_off = d_key_off;
+    P.n = n;
+    P.key_bytes = key_bytes;
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    HIP_TRY(launch_bloom_add(P, false, s));
+    return RIO_OK;
+}
+
+extern "C" int rio_sst_bloom_add(rio_ctx* ctx, const rio_bloom_view* f, const uint64_t* d_out_src, uint64_t n_out,
+                                 void* stream) {
+    if (!ctx || !bloom_view_ok(f) || (n_out && (!f->bits || !f->hash_keys || !d_out_src))) return RIO_ERR_ARG;
+    // from here on *ctx is read
+    if (!ctx->mrg_planned) return RIO_ERR_STATE;
+    if (n_out > ctx->mrg_N) return RIO_ERR_ARG;
+    if (n_out == 0) return RIO_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    BloomParams P{};
+    P.f = *f;
+    P.n = n_out;
+    P.views = ctx->mrg_views.as<rio_sst_view>();
+    P.T = ctx->mrg_T;
+    P.out_src = d_out_src;
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    HIP_TRY(launch_bloom_add(P, true, s));
+    return RIO_OK;
+}
+
+extern "C" int rio_bloom_contains(rio_ctx* ctx, const rio_bloom_view* f, const uint8_t* d_keys, const uint64_t* d_key_off,
+                                  uint64_t n, uint64_t key_bytes, uint8_t* d_hit, void* stream) {
+    if (!ctx || !bloom_view_ok(f)) return RIO_ERR_ARG;
+    if (n == 0) return RIO_OK;
+    if (!f->bits || !f->hash_keys || !d_keys || !d_key_off || !d_hit) return RIO_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    BloomParams P{};
+    P.f = *f;
+    P.keys = d_keys;
+    P.key_off = d_key_off;
+    P.n = n;
+    P.key_bytes = key_bytes;
+    P.hit = d_hit;
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    HIP_TRY(launch_bloom_contains(P, s));
+    return RIO_OK;
+}
+
+extern "C" int rio_sst_key_prefixes(rio_ctx* ctx, const rio_sst_view* view, uint64_t* d_pfx, void* stream) {
+    if (!ctx || !view) return RIO_ERR_ARG;
+    if (view->n == 0) return RIO_OK;
+    if (!d_pfx || !view->index || !view->key_off || !view->key_len) return RIO_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    HIP_TRY(launch_sst_key_prefixes(*view, d_pfx, s));
+    return RIO_OK;
+}
+
+extern "C" int rio_sst_lookup(rio_ctx* ctx, const rio_sst_view* view, const uint64_t* d_pfx, const rio_bloom_view* f,
+                              const uint8_t* d_keys, const uint64_t* d_key_off, uint64_t n, uint64_t key_bytes,
+                              uint64_t* d_entry, void* stream) {
+    if (!ctx || !view || (f && !bloom_view_ok(f))) return RIO_ERR_ARG;
+    if (n == 0) return RIO_OK;
+    if (!d_keys || !d_key_off || !d_entry || (f && (!f->bits || !f->hash_keys)) ||
+        (view->n && (!d_pfx || !view->index || !view->key_off || !view->key_len)))
+        return RIO_ERR_ARG;
+    HIP_TRY(hipSetDevice(ctx->device));
+    BloomParams P{};
+    if (f) P.f = *f;  // bits stays null without a gate
+    P.keys = d_keys;
+    P.key_off = d_key_off;
+    P.n = n;
+    P.key_bytes = key_bytes;
+    LookupParams Q{};
+    Q.v = *view;
+    Q.pfx = d_pfx;
+    Q.entry = d_entry;
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    HIP_TRY(launch_sst_lookup(P, Q, s));
     return RIO_OK;
 }
 

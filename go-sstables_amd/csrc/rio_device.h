@@ -270,6 +270,26 @@ struct WalParams {
     uint64_t* op_rec;             // [n_ops] or null
 };
 
+// rio_bloom.hip: bloom filter build / query and the point lookup of a loaded table (rio_bloom_*, rio_sst_lookup)
+struct BloomParams {
+    rio_bloom_view f;             // the filter (bits == null: rio_sst_lookup without a gate)
+    // keys of an arena (rio_bloom_add / rio_bloom_contains / rio_sst_lookup's queries)
+    const uint8_t* keys;
+    const uint64_t* key_off;      // [n + 1]
+    uint64_t n;
+    uint64_t key_bytes;           // arena length: every key is clamped to it
+    // keys of the last plan's survivors (rio_sst_bloom_add): n survivors
+    const rio_sst_view* views;
+    uint32_t T;
+    const uint64_t* out_src;      // [n]
+    uint8_t* hit;                 // [n] rio_bloom_contains
+};
+struct LookupParams {
+    rio_sst_view v;               // the table, by value: nothing is copied to the device beforehand
+    const uint64_t* pfx;          // [v.n] rio_sst_key_prefixes
+    uint64_t* entry;              // [n] entry index or ~0
+};
+
 // protobuf varint length, and proto.Marshal's size of an IndexEntry {key = 1, valueOffset = 2, checksum = 3}:
 // proto3 omits an empty key and zero scalars (sstables/proto/sstable.proto:5-9)
 #ifdef __HIPCC__

@@ -35,12 +35,12 @@ def _f32(x: float) -> float:
 
 
 def flush_ops_on_device(ctx, device: int, ops_view, mode: int, comp: int, mark=None,
-                        max_key_len: int = L.RIO_FLUSH_MAX_KEY_LEN):
+                        max_key_len: int = L.RIO_FLUSH_MAX_KEY_LEN, flt=None):
     """rio_sst_flush_plan over a device-resident op log (an OpsView), then gather, data encode, index
     entries and index encode on torch's current stream; returns the merger's Compaction (status "unsorted"
     with unsorted_table = the first rejected op when the log is inconsistent or a key is longer than
     max_key_len). max_key_len bounds the key lengths and sets the sort's pass count: pass the longest key's
-    length. `mark(name)` as for sstables.merger.compact_on_device."""
+    length. `mark(name)` and `flt` (the table's bloom filter to build) as for sstables.merger.compact_on_device."""
     import torch
 
     from sstables.merger import check_status, encode_planned, on_device_stream
@@ -56,7 +56,7 @@ def flush_ops_on_device(ctx, device: int, ops_view, mode: int, comp: int, mark=N
         check_status(L.lib().rio_sst_flush_plan(ctx, ctypes.addressof(ops_view), mode, max_key_len, src.data_ptr(),
                                           keep.data_ptr(), res.data_ptr(), st), "rio_sst_flush_plan")
         mark("plan")
-        return encode_planned(ctx, device, st, src, keep, res, comp, mark, False)
+        return encode_planned(ctx, device, st, src, keep, res, comp, mark, False, flt)
 
     return on_device_stream(device, run)
 
@@ -186,7 +186,7 @@ class MemStore:
         import numpy as np
         import torch
 
-        from sstables import UnsupportedError, _WriterOpts
+        from sstables import UnsupportedError, _WriterOpts, writer_filter
         from sstables.merger import write_table_files
 
         o = _WriterOpts()
@@ -196,6 +196,9 @@ class MemStore:
             return GoError("basePath was not supplied")  # sstable_writer.go:232
         if o.dataCompressionType not in (L.COMP_NONE, L.COMP_SNAPPY):
             return UnsupportedError(f"output data compression {o.dataCompressionType}: the device encodes none and snappy")
+        flt, err = writer_filter(o)  # sstable_writer.go:239-241, :78-83
+        if err is not None:
+            return err
         if self._max_key_len > L.RIO_FLUSH_MAX_KEY_LEN:
             return UnsupportedError(f"a key of {self._max_key_len} bytes: the device flush orders keys of up to "
                                     f"{L.RIO_FLUSH_MAX_KEY_LEN}")
@@ -213,7 +216,7 @@ class MemStore:
                              val_off=val_off.data_ptr(), flags=flags.data_ptr(), n=n, key_bytes=len(self._keys),
                              value_bytes=len(self._values))
             c = flush_ops_on_device(L.default_ctx(self.device), self.device, view, mode, o.dataCompressionType,
-                                    max_key_len=self._max_key_len)
+                                    max_key_len=self._max_key_len, flt=flt)
             if c.status is not None:
                 return GoError(f"memstore flush '{o.basePath}': op {c.unsorted_table} of the log was rejected")
             lo = hi = b""

@@ -113,6 +113,20 @@ class SstView(ctypes.Structure):
     ]
 
 
+RIO_BLOOM_MAX_K = 64
+
+
+class BloomView(ctypes.Structure):
+    """rio_bloom_view (include/rio.h): a filter's bits and hash keys on the device."""
+
+    _fields_ = [
+        ("bits", c_void_p),
+        ("hash_keys", c_void_p),
+        ("m", c_uint64),
+        ("k", c_uint32),
+    ]
+
+
 RIO_FLUSH_WITH_TOMBSTONES, RIO_FLUSH_SKIP_TOMBSTONES = 0, 1
 RIO_FLUSH_MAX_KEY_LEN = 1024
 
@@ -278,6 +292,13 @@ _SIGS = {
     "rio_sst_index_encode": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p]),
     "rio_index_entry_len": (c_uint64, [c_uint64, c_uint64, c_uint64]),
     "rio_index_entries_bound": (c_uint64, [c_uint64, c_uint64]),
+    "rio_bloom_optimal": (c_int, [c_uint64, ctypes.c_double, POINTER(c_uint64), POINTER(c_uint64)]),
+    "rio_bloom_add": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p]),
+    "rio_sst_bloom_add": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p]),
+    "rio_bloom_contains": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p]),
+    "rio_sst_key_prefixes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rio_sst_lookup": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p]),
     "rio_sst_flush_plan": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rio_sst_flush_stage_ms": (c_int, [c_void_p, POINTER(c_float), c_int]),
     "rio_wal_ops_plan": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),

@@ -104,22 +104,34 @@ def wal_ops_on_device(ctx, device: int, segments, mark=None):
     return on_device_stream(device, run)
 
 
-def recover_wal(base_path: str, table_path: str, device: int = 0, compression: int = L.COMP_SNAPPY):
+def recover_wal(base_path: str, table_path: str, device: int = 0, compression: int = L.COMP_SNAPPY,
+                bloom_filter: bool = False, bloom_fp_probability: float = 0.01):
     """Replay the WAL directory `base_path` into one SSTable at `table_path` (FlushWithTombstones), then
     empty the directory (recovery.go:208-268). Returns (num_records, wrote_table, err). The error is the
     earliest in replay order, with wal.Replayer's texts and wrapping; on any error no table is written and the
     directory is left untouched. No table is written when no record holds an op (executeFlush skips an empty
-    memstore, flush.go:37)."""
+    memstore, flush.go:37). bloom_filter: also write the table's bloom.bf.gz, sized for the memstore's
+    size (its distinct keys), as executeFlush sizes it (flush.go:35,55); off by default here."""
     import torch
 
     from memstore import flush_ops_on_device
     from recordio.device import DeviceDecoder, to_device_file
-    from sstables import UnsupportedError
+    from sstables import UnsupportedError, _WriterOpts, writer_filter
     from sstables.merger import write_table_files
     from wal import _wal_files
 
     if compression not in (L.COMP_NONE, L.COMP_SNAPPY):
         return 0, False, UnsupportedError(f"output data compression {compression}: the device encodes none and snappy")
+    flt = None
+    if bloom_filter:
+        _, err = writer_filter(_WriterOpts(basePath=table_path, enableBloomFilter=True,
+                                           bloomFpProbability=bloom_fp_probability))
+        if err is not None:  # a probability NewOptimal refuses, before anything is read
+            return 0, False, err
+
+        def flt(n_out):  # FlushWithTombstones keeps every key of the memstore: n_out is its size
+            return writer_filter(_WriterOpts(basePath=table_path, enableBloomFilter=True, bloomExpectedNumberOfElements=n_out,
+                                             bloomFpProbability=bloom_fp_probability))[0]
     try:
         paths = _wal_files(base_path)
     except OSError as e:
@@ -178,7 +190,8 @@ def recover_wal(base_path: str, table_path: str, device: int = 0, compression: i
             if max_key > L.RIO_FLUSH_MAX_KEY_LEN:
                 return n_records, False, UnsupportedError(
                     f"a key of {max_key} bytes: the device flush orders keys of up to {L.RIO_FLUSH_MAX_KEY_LEN}")
-            c = flush_ops_on_device(ctx, device, t["view"], L.RIO_FLUSH_WITH_TOMBSTONES, compression, max_key_len=max_key)
+            c = flush_ops_on_device(ctx, device, t["view"], L.RIO_FLUSH_WITH_TOMBSTONES, compression, max_key_len=max_key,
+                                    flt=flt)
             if c.status is not None:
                 return n_records, False, GoError(f"memstore flush '{table_path}': op {c.unsorted_table} of the log was rejected")
             ends = [int(x) & _NONE for x in c.out_src[[0, c.n_out - 1]].cpu().tolist()]

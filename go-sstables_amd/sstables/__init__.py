@@ -21,7 +21,7 @@ from dataclasses import dataclass
 from recordio import _lib as L
 from recordio.errors import EOF, ErrCorrupt, GoError, wrap
 
-from . import proto
+from . import bloom, proto
 from .disk_index import DiskIndexLoader, DiskKeyIndex, IndexVal  # noqa: F401
 from .writer import NewSSTableStreamWriter, SSTableStreamWriter, write_sstable  # noqa: F401
 
@@ -94,6 +94,11 @@ def ReadOnDevice(device: int):  # noqa: N802
 class _WriterOpts:
     basePath: str = ""
     dataCompressionType: int = L.COMP_SNAPPY  # sstable_writer.go:219-220
+    # the reference enables the filter by default (sstable_writer.go:218); here it is off unless enabled
+    # (DESIGN.md §10), the two sizes are the reference's defaults (:221-222)
+    enableBloomFilter: bool = False
+    bloomExpectedNumberOfElements: int = 1000
+    bloomFpProbability: float = 0.01
 
 
 def WriteBasePath(p: str):  # noqa: N802
@@ -106,6 +111,39 @@ def DataCompressionType(c: int):  # noqa: N802
     """sstable_writer.go:283; the device encodes recordio's none and snappy."""
     def f(o): o.dataCompressionType = c
     return f
+
+
+def EnableBloomFilter():  # noqa: N802
+    """sstable_writer.go:289: write bloom.bf.gz next to the table's three files."""
+    def f(o): o.enableBloomFilter = True
+    return f
+
+
+def BloomExpectedNumberOfElements(n: int):  # noqa: N802
+    """sstable_writer.go:295."""
+    def f(o): o.bloomExpectedNumberOfElements = n
+    return f
+
+
+def BloomFalsePositiveProbability(p: float):  # noqa: N802
+    """sstable_writer.go:301."""
+    def f(o): o.bloomFpProbability = p
+    return f
+
+
+def writer_filter(o: _WriterOpts, device_limits: bool = True):
+    """The filter a writer with options `o` builds -> (Filter or None when not enabled, err): the check of
+    NewSSTableStreamWriter (sstable_writer.go:239-241), then NewOptimal as Open does (:78-83)."""
+    if not o.enableBloomFilter:
+        return None, None
+    if o.bloomExpectedNumberOfElements <= 0:
+        return None, GoError(f"unexpected number of bloom filter elements, was: {o.bloomExpectedNumberOfElements}")
+    f, err = bloom.NewOptimal(o.bloomExpectedNumberOfElements, o.bloomFpProbability)
+    if err is not None:
+        return None, wrap(f"error while creating bloomfilter in '{o.basePath}'", err)
+    if device_limits and f.k > L.RIO_BLOOM_MAX_K:
+        return None, UnsupportedError(f"a bloom filter of {f.k} probes: the device builds up to {L.RIO_BLOOM_MAX_K}")
+    return f, None
 
 
 def _fmt_key(k: bytes) -> str:
@@ -225,9 +263,11 @@ class _DeviceTable:
 
 
 class SSTableReader:
-    def __init__(self, opts: _Opts, meta: proto.MetaData, table: _DeviceTable):
+    def __init__(self, opts: _Opts, meta: proto.MetaData, table: _DeviceTable, bloom_filter=None):
         self.opts, self.meta, self.t = opts, meta, table
+        self.bloomFilter = bloom_filter  # host copy of bloom.bf.gz, None when the table has none
         self._keys = None
+        self._pfx = self._dfilter = None  # device key prefixes / filter, built at the first batched lookup
 
     def MetaData(self) -> proto.MetaData:  # noqa: N802
         return self.meta
@@ -298,14 +338,70 @@ class SSTableReader:
         return self._value_at(i, self.opts.skipHashCheckOnRead)
 
     def Contains(self, key: bytes):  # noqa: N802
+        """sstable_reader.go:49-65: the filter first when the table has one, then the index."""
         import bisect
 
+        if self.bloomFilter is not None and not self.bloomFilter.Contains(bytes(key)):
+            return False, None
         ks = self._index_keys()
         i = bisect.bisect_left(ks, bytes(key))
         return i < len(ks) and ks[i] == bytes(key), None
 
+    def _lookup(self, keys, gated: bool):
+        """Entry index (or _NONE) per query key: one upload of the query arena, rio_sst_lookup over the
+        table's resident keys (rio_bloom.hip; gated by the table's filter or not), one read-back."""
+        import numpy as np
+        import torch
+
+        from .merger import check_status, on_device_stream, table_view
+
+        keys = [bytes(k) for k in keys]
+        n = len(keys)
+        if n == 0:
+            return []
+        t, device = self.t, self.opts.device
+        dev = f"cuda:{device}"
+        lib, ctx = L.lib(), L.default_ctx(device)
+        arena = b"".join(keys)
+        off = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum([len(k) for k in keys], out=off[1:])
+        view = table_view(t)
+        with torch.cuda.device(device):
+            def run(st):
+                if self._pfx is None:  # once per reader: the table's keys do not change
+                    self._pfx = torch.empty(max(t.n_index, 1), dtype=torch.int64, device=dev)
+                    check_status(lib.rio_sst_key_prefixes(ctx, ctypes.byref(view), self._pfx.data_ptr(), st),
+                                 "rio_sst_key_prefixes")
+                if gated and self.bloomFilter is not None and self._dfilter is None:
+                    self._dfilter = self.bloomFilter.on_device(device)
+                f = self._dfilter.ref() if gated and self.bloomFilter is not None else None
+                d_keys = torch.from_numpy(np.frombuffer(arena + b"\0", dtype=np.uint8).copy()).to(dev)
+                d_off = torch.from_numpy(off).to(dev)
+                d_entry = torch.empty(n, dtype=torch.int64, device=dev)
+                check_status(lib.rio_sst_lookup(ctx, ctypes.byref(view), self._pfx.data_ptr(), f, d_keys.data_ptr(),
+                                                d_off.data_ptr(), n, len(arena), d_entry.data_ptr(), st), "rio_sst_lookup")
+                return d_entry
+
+            d_entry = on_device_stream(device, run)
+            return [int(x) & _NONE for x in d_entry.cpu().tolist()]
+
+    def ContainsBatch(self, keys):  # noqa: N802
+        """[(found, err)] per key: what a loop of Contains returns (filter gate, then the index), in one
+        device lookup."""
+        if self.bloomFilter is not None and self.bloomFilter.k > L.RIO_BLOOM_MAX_K:
+            err = UnsupportedError(f"a bloom filter of {self.bloomFilter.k} probes: the device takes up to "
+                                   f"{L.RIO_BLOOM_MAX_K}")
+            return [(False, err) for _ in keys]
+        return [(i != _NONE, None) for i in self._lookup(keys, True)]
+
+    def GetBatch(self, keys):  # noqa: N802
+        """[(value, err)] per key: what a loop of Get returns (no filter, sstable_reader.go:67-77), the
+        search in one device lookup, values and per-entry errors as Get's."""
+        return [(None, NotFound) if i == _NONE else self._value_at(i, self.opts.skipHashCheckOnRead)
+                for i in self._lookup(keys, False)]
+
     def Close(self):  # noqa: N802
-        self.t = None
+        self.t = self._pfx = self._dfilter = None
         return None
 
 
@@ -381,7 +477,14 @@ def NewSSTableReader(*options):  # noqa: N802
                              f"invalid wire-format data (record {t.bad_proto})")
     if t.unplaced != _NONE:
         return None, UnsupportedError(f"sstable '{o.basePath}': index entry {t.unplaced} is not in the writer's layout")
-    r = SSTableReader(o, meta, t)
+    # readFilterIfExists (sstable_reader.go:296-299, 343-353; "filterin" is the reference's text)
+    flt, fpath = None, os.path.join(o.basePath, BloomFileName)
+    if os.path.exists(fpath):
+        flt, err = bloom.ReadFile(fpath)
+        if err is not None:
+            return None, wrap(f"error while reading filter of sstable in '{o.basePath}'",
+                              wrap(f"error while reading bloom filterin '{fpath}'", err))
+    r = SSTableReader(o, meta, t, flt)
     # validateDataFile returns at once for v0 tables (sstable_reader.go:205-209)
     if not v0 and not o.skipHashCheckOnLoad and (t.bad_crc != _NONE or t.value_bad != _NONE):
         # validateDataFile stops at the first entry whose value fails to read or to hash; a value

@@ -16,7 +16,7 @@ import os
 from recordio import _lib as L
 from recordio.errors import GoError
 
-from . import proto
+from . import bloom, proto
 
 _NONE = 0xFFFFFFFFFFFFFFFF
 _ENTRY_MASK = (1 << L.RIO_MERGE_ENTRY_BITS) - 1
@@ -66,6 +66,7 @@ class Compaction:
     n_out = value_bytes = null_values = key_bytes = 0
     first_dup = unsorted_table = _NONE
     out_src = data_img = data_len = index_img = index_len = None
+    bloom = None  # (host Filter, DeviceFilter) when the table gets a bloom.bf.gz
 
 
 def on_device_stream(device: int, fn):
@@ -90,10 +91,13 @@ def check_status(rc, what):
         raise GoError(f"{what}: {L.strerror(rc)}")
 
 
-def encode_planned(ctx, device: int, st, src, keep, res, comp: int, mark, refuse_dup: bool) -> Compaction:
+def encode_planned(ctx, device: int, st, src, keep, res, comp: int, mark, refuse_dup: bool, flt=None) -> Compaction:
     """What follows a plan (rio_sst_merge_plan or rio_sst_flush_plan, whose view the context holds): result
-    read, gather, data encode, index entries, index encode, on stream `st`. src / keep / res are the plan's
-    outputs. Shared by compact_on_device and memstore.flush_ops_on_device."""
+    read, gather, [filter build,] data encode, index entries, index encode, on stream `st`. src / keep / res
+    are the plan's outputs. Shared by compact_on_device and memstore.flush_ops_on_device.
+    flt: None, an empty sstables.bloom.Filter (sstables.writer_filter), or a callable n_out -> Filter: its
+    bits are built on the device from the survivors' keys (rio_sst_bloom_add: one Add per WriteNext,
+    sstable_writer.go:114-118) and fetched with the file images by write_table_files."""
     import torch
 
     lib = L.lib()
@@ -118,6 +122,16 @@ def encode_planned(ctx, device: int, st, src, keep, res, comp: int, mark, refuse
     check_status(lib.rio_sst_merge_gather(ctx, src.data_ptr(), keep.data_ptr(), n, c.out_src.data_ptr(), values.data_ptr(),
                                     values.numel(), val_off.data_ptr(), val_flags.data_ptr(), st), "rio_sst_merge_gather")
     mark("gather")
+    if flt is not None:
+        if callable(flt):
+            flt = flt(n)
+        # zero-filled bits and the hash keys go up; nothing comes back before the files are fetched
+        words = torch.zeros((flt.m + 63) // 64, dtype=torch.int64, device=dev)
+        hk = torch.tensor([x - (1 << 64) if x >> 63 else x for x in flt.keys], dtype=torch.int64).to(dev, non_blocking=True)
+        d = bloom.DeviceFilter(words, hk, flt.m, flt.k)
+        check_status(lib.rio_sst_bloom_add(ctx, d.ref(), c.out_src.data_ptr(), n, st), "rio_sst_bloom_add")
+        c.bloom = (flt, d)
+        mark("bloom")
     cap = int(lib.rio_encode_bound(n, c.value_bytes, comp))
     c.data_img, data_rec_off, c.data_len = u8(cap), i64(n), i64(1)
     check_status(lib.rio_device_encode(ctx, values.data_ptr(), val_off.data_ptr(), val_flags.data_ptr(), n, c.value_bytes, comp,
@@ -140,10 +154,11 @@ def encode_planned(ctx, device: int, st, src, keep, res, comp: int, mark, refuse
     return c
 
 
-def compact_on_device(ctx, device: int, views, mode: int, comp: int, mark=None) -> Compaction:
+def compact_on_device(ctx, device: int, views, mode: int, comp: int, mark=None, flt=None) -> Compaction:
     """Plan, gather, data encode, index entries, index encode on torch's current stream. `views` is a
     ctypes array of SstView. `mark(name)` is called after each stage is enqueued and after each of the two
-    host reads (benchmarks record an event there, so the host gaps are intervals of their own). The file images stay on the device; data_len / index_len are 1-element tensors."""
+    host reads (benchmarks record an event there, so the host gaps are intervals of their own). The file images stay on the device; data_len / index_len are 1-element tensors.
+    flt: the table's bloom filter to build, as for encode_planned."""
     import torch
 
     mark = mark or (lambda name: None)
@@ -157,14 +172,15 @@ def compact_on_device(ctx, device: int, views, mode: int, comp: int, mark=None) 
         check_status(L.lib().rio_sst_merge_plan(ctx, ctypes.addressof(views), len(views), mode, src.data_ptr(), keep.data_ptr(),
                                           res.data_ptr(), st), "rio_sst_merge_plan")
         mark("plan")
-        return encode_planned(ctx, device, st, src, keep, res, comp, mark, mode == L.RIO_MERGE_ALL)
+        return encode_planned(ctx, device, st, src, keep, res, comp, mark, mode == L.RIO_MERGE_ALL, flt)
 
     return on_device_stream(device, run)
 
 
 def write_table_files(path: str, c: Compaction, min_key: bytes, max_key: bytes):
-    """data.rio, index.rio and meta.pb.bin of a finished Compaction (its images are fetched here)."""
-    from . import DataFileName, IndexFileName, MetaFileName
+    """data.rio, index.rio and meta.pb.bin of a finished Compaction (its images are fetched here), and
+    bloom.bf.gz when the compaction built a filter (header n = numRecords: one Add per written key)."""
+    from . import BloomFileName, DataFileName, IndexFileName, MetaFileName
 
     dn, ixn = int(c.data_len.item()), int(c.index_len.item())
     data = bytes(c.data_img[:dn].cpu().numpy())
@@ -177,6 +193,12 @@ def write_table_files(path: str, c: Compaction, min_key: bytes, max_key: bytes):
     for name, b in ((DataFileName, data), (IndexFileName, index), (MetaFileName, meta.marshal())):
         with open(os.path.join(path, name), "wb") as fh:
             fh.write(b)
+    if c.bloom is not None:
+        flt, d = c.bloom
+        out = bloom.Filter(flt.m, flt.keys, bytearray(d.bits.cpu().numpy().tobytes()), c.n_out)
+        err = out.WriteFile(os.path.join(path, BloomFileName))
+        if err is not None:
+            raise err
 
 
 class SSTableMerger:
@@ -184,26 +206,35 @@ class SSTableMerger:
         """comp: bytes comparator only (skiplist.BytesComparator, the reference's default)."""
         self.data_compression = data_compression
 
-    def Merge(self, readers, writer_path: str, data_compression=None):  # noqa: N802
+    def Merge(self, readers, writer_path: str, data_compression=None, writer_options=()):  # noqa: N802
         """SSTableMerger.Merge (sstable_merger.go:41-68): every entry of every table, nil values too. Two
         tables holding one key give WriteNext's error; no file is written then (the reference leaves the
-        table written up to that key behind)."""
-        return self._run(readers, writer_path, L.RIO_MERGE_ALL, data_compression)
+        table written up to that key behind). writer_options: the output writer's bloom options
+        (sstables.EnableBloomFilter, BloomExpectedNumberOfElements, BloomFalsePositiveProbability)."""
+        return self._run(readers, writer_path, L.RIO_MERGE_ALL, data_compression, writer_options)
 
-    def MergeCompact(self, readers, writer_path: str, reduce, data_compression=None):  # noqa: N802
+    def MergeCompact(self, readers, writer_path: str, reduce, data_compression=None, writer_options=()):  # noqa: N802
         """SSTableMerger.MergeCompact (sstable_merger.go:146-165) with one of the reference's reducers;
-        the reader's position in `readers` is its context (super_sstable_reader.go:88-97)."""
+        the reader's position in `readers` is its context (super_sstable_reader.go:88-97). writer_options as
+        for Merge (simpledb/compaction.go:79 sizes the filter for every compaction)."""
         from . import UnsupportedError
 
         if not isinstance(reduce, _Reducer):
             return UnsupportedError("MergeCompact on the device runs ScanReduceLatestWins / "
                                     "ScanReduceLatestWinsSkipTombstones only")
-        return self._run(readers, writer_path, reduce.mode, data_compression)
+        return self._run(readers, writer_path, reduce.mode, data_compression, writer_options)
 
-    def _run(self, readers, path, mode, comp):
+    def _run(self, readers, path, mode, comp, writer_options=()):
         import torch
 
-        from . import SSTableReader, UnsupportedError
+        from . import SSTableReader, UnsupportedError, _WriterOpts, writer_filter
+
+        o = _WriterOpts(basePath=path)
+        for f in writer_options:
+            f(o)
+        flt, err = writer_filter(o)
+        if err is not None:
+            return err
 
         comp = self.data_compression if comp is None else comp
         if comp not in (L.COMP_NONE, L.COMP_SNAPPY):
@@ -231,7 +262,7 @@ class SSTableMerger:
         device = readers[0].opts.device
         views = (L.SstView * len(readers))(*[table_view(r.t) for r in readers])
         with torch.cuda.device(device):
-            c = compact_on_device(L.default_ctx(device), device, views, mode, comp)
+            c = compact_on_device(L.default_ctx(device), device, views, mode, comp, flt=flt)
             if c.status == "unsorted":
                 return UnsupportedError(f"sstable '{readers[c.unsorted_table].opts.basePath}': keys are not strictly "
                                         "ascending")

@@ -1,7 +1,8 @@
 """SSTableStreamWriter mirror (sstables/sstable_writer.go:27-180): the input generator for the
 device scan. data.rio = one recordio v4 record per value (Snappy by default, :219-220), index.rio =
 one IndexEntry{key, valueOffset, checksum = CRC-64/ISO of the value} per key (uncompressed), and
-meta.pb.bin. Host-side; the bloom filter (optional in the reference) is not written.
+meta.pb.bin, and bloom.bf.gz when a filter is given (sstables.bloom; one Add per key, :114-118, written at
+Close, :150-154). Host-side. Unlike the reference's writer the filter is off unless asked for.
 """
 from __future__ import annotations
 
@@ -64,8 +65,10 @@ class _Image:
 
 
 class SSTableStreamWriter:
-    def __init__(self, base_path: str, data_compression: int = 2, index_compression: int = 0):
+    def __init__(self, base_path: str, data_compression: int = 2, index_compression: int = 0, bloom_filter=None):
+        """bloom_filter: an empty sstables.bloom.Filter (sstables.writer_filter of the writer options), or None."""
         self.base = base_path
+        self.bloomFilter = bloom_filter
         self.data = _Image(data_compression)
         self.index = _Image(index_compression)
         self.meta = MetaData(version=1)
@@ -86,6 +89,8 @@ class SSTableStreamWriter:
         else:
             self.meta.minKey = key
         self.last = key
+        if self.bloomFilter is not None:
+            self.bloomFilter.Add(key)
         vb = b"" if value is None else bytes(value)
         cs = self._crc_cache.get(vb)
         if cs is None:
@@ -100,9 +105,13 @@ class SSTableStreamWriter:
         return None
 
     def Close(self):  # noqa: N802
-        from . import DataFileName, IndexFileName, MetaFileName
+        from . import BloomFileName, DataFileName, IndexFileName, MetaFileName
 
         d, i = self.data.bytes(), self.index.bytes()
+        if self.bloomFilter is not None:
+            err = self.bloomFilter.WriteFile(os.path.join(self.base, BloomFileName))
+            if err is not None:
+                return GoError(f"error in writing bloom filter  in '{self.base}': {err}", err)
         with open(os.path.join(self.base, DataFileName), "wb") as fh:
             fh.write(d)
         with open(os.path.join(self.base, IndexFileName), "wb") as fh:
@@ -115,13 +124,24 @@ class SSTableStreamWriter:
         return None
 
 
-def NewSSTableStreamWriter(base_path: str, data_compression: int = 2):  # noqa: N802
-    return SSTableStreamWriter(base_path, data_compression), None
+def NewSSTableStreamWriter(base_path: str, data_compression: int = 2, writer_options=()):  # noqa: N802
+    """writer_options: sstables.EnableBloomFilter / BloomExpectedNumberOfElements / BloomFalsePositiveProbability."""
+    from . import _WriterOpts, writer_filter
+
+    o = _WriterOpts(basePath=base_path)
+    for f in writer_options:
+        f(o)
+    flt, err = writer_filter(o, device_limits=False)
+    if err is not None:
+        return None, err
+    return SSTableStreamWriter(base_path, data_compression, bloom_filter=flt), None
 
 
-def write_sstable(base_path: str, items, data_compression: int = 2) -> MetaData:
+def write_sstable(base_path: str, items, data_compression: int = 2, writer_options=()) -> MetaData:
     """Write sorted (key, value) pairs as one table; returns its MetaData."""
-    w = SSTableStreamWriter(base_path, data_compression)
+    w, err = NewSSTableStreamWriter(base_path, data_compression, writer_options)
+    if err is not None:
+        raise err
     w.Open()
     for k, v in items:
         err = w.WriteNext(k, v)

@@ -24,6 +24,10 @@
  *   NewSSTableReader load / validateDataFile / Scan (rio_sst_*)   sstables/sstable_reader.go:250-345, 205-238, 119-159
  *   DiskKeyIndex binarySearch (rio_index_*)                       sstables/disk_key_index.go:87-140
  *   wal.Replayer.Replay (rio_replay_*)                            wal/replayer.go:18-77
+ *   SSTableStreamWriter's bloom filter: NewOptimal / Add          sstables/sstable_writer.go:78-83, 114-118, 150-154
+ *     (rio_bloom_optimal, rio_bloom_add, rio_sst_bloom_add)
+ *   SSTableReader.Contains / Get, SliceKeyIndex.Get in batches    sstables/sstable_reader.go:49-77,
+ *     (rio_bloom_contains, rio_sst_key_prefixes, rio_sst_lookup)  sstables/slice_key_index.go:19-35
  *   FileWriter.Write + fillRecordHeaderV4 (input generator only)  recordio/file_writer.go:160-233
  */
 #ifndef RIO_H
@@ -528,6 +532,59 @@ int rio_wal_ops_plan(rio_ctx* ctx, const rio_wal_segment* segs, uint32_t n_segs,
 int rio_wal_ops_gather(rio_ctx* ctx, uint64_t n_ops, uint8_t* d_keys, uint64_t keys_cap, uint64_t* d_key_off,
                        uint8_t* d_values, uint64_t values_cap, uint64_t* d_val_off, uint8_t* d_flags,
                        uint64_t* d_op_rec /* may be NULL: source record index of each op */, void* stream);
+
+/* ---- bloom filters of tables, and point lookups of a loaded table (rio_bloom.hip) --------------
+ * Replaces the writer's filter build (sstables/sstable_writer.go:78-83 NewOptimal, :114-118 one Add per
+ * WriteNext, :150-154 WriteFile) and the reader's point lookups (sstable_reader.go:49-65 Contains: filter
+ * first, then the index; :67-77 Get; slice_key_index.go:19-35 the search) with batched calls over keys that
+ * are already in HBM. The filter is steakknife/bloomfilter's: m bits, k 64-bit hash keys; an element is the
+ * FNV-1 64-bit hash h of the key (hash/fnv New64: basis 0xcbf29ce484222325, per byte h *= 0x100000001b3 then
+ * h ^= byte); probe j is bit (h ^ hash_keys[j]) mod m, bit i being bit i & 63 of 64-bit word i >> 6. Add sets
+ * all k bits, Contains needs all k. The file around the bits (gzip, header, SHA-384 trailer) is host work.
+ *   bits       8 * ceil(m / 64) bytes of device memory, little-endian 64-bit words as the file holds them
+ *   hash_keys  [k] device array
+ * All calls are stream-ordered (NULL = the ctx stream), never synchronise with the host and allocate
+ * nothing: they can be captured into a hipGraph. Every offset read from a buffer is clamped to its arena and
+ * every entry index to its table: a wrong input gives wrong answers or ~0, never an out-of-range access.
+ * RIO_ERR_ARG before any device call and before *ctx is read: a NULL ctx or filter, k = 0, k > RIO_BLOOM_MAX_K,
+ * m < 2, and with n > 0 a NULL array (bits and hash_keys included). n = 0 is a no-op returning RIO_OK. */
+#define RIO_BLOOM_MAX_K 64u
+typedef struct rio_bloom_view {
+    uint64_t* bits;
+    const uint64_t* hash_keys;
+    uint64_t m;
+    uint32_t k;
+} rio_bloom_view;
+/* bloomfilter.NewOptimal's sizes (host): m = ceil(-max_n * ln p / ln^2 2), k = ceil(ln 2 * m / max_n);
+ * (1000, 0.01) -> (9586, 7), the writer's defaults (sstable_writer.go:218-222). RIO_ERR_ARG for max_n = 0,
+ * p outside (0, 1) or a NULL output. *k may exceed RIO_BLOOM_MAX_K for a tiny p: the device calls refuse it. */
+int rio_bloom_optimal(uint64_t max_n, double p, uint64_t* m, uint64_t* k);
+/* filter.Add(fnv64(key)) for key i = d_keys[d_key_off[i] .. d_key_off[i + 1]), i < n (sstable_writer.go:114-118).
+ * ORs into the bits that are there: the caller zero-fills, several adds compose. key_bytes is the arena's
+ * length; nothing past it is read. */
+int rio_bloom_add(rio_ctx* ctx, const rio_bloom_view* f, const uint8_t* d_keys, const uint64_t* d_key_off, uint64_t n,
+                  uint64_t key_bytes, void* stream);
+/* The same for the keys of the last plan's survivors (rio_sst_merge_plan or rio_sst_flush_plan on this
+ * context): d_out_src [n_out] as rio_sst_merge_gather leaves it, the keys found as rio_sst_index_encode finds
+ * them. RIO_ERR_STATE without a plan (checked before the n_out = 0 no-op), RIO_ERR_ARG for n_out above the
+ * plan's entry count. */
+int rio_sst_bloom_add(rio_ctx* ctx, const rio_bloom_view* f, const uint64_t* d_out_src, uint64_t n_out, void* stream);
+/* filter.Contains(fnv64(key)) per key (sstable_reader.go:51-60): d_hit[i] = 1 when all k bits are set, else 0. */
+int rio_bloom_contains(rio_ctx* ctx, const rio_bloom_view* f, const uint8_t* d_keys, const uint64_t* d_key_off,
+                       uint64_t n, uint64_t key_bytes, uint8_t* d_hit, void* stream);
+/* First 8 key bytes of every entry of a loaded table, big-endian and zero-padded, into the caller's
+ * d_pfx[view->n]: what rio_sst_lookup probes. A reader builds it once per table (the merge plan's own
+ * prefixes live in plan scratch and do not survive the plan). */
+int rio_sst_key_prefixes(rio_ctx* ctx, const rio_sst_view* view, uint64_t* d_pfx, void* stream);
+/* SliceKeyIndex.Get / Contains per query key (slice_key_index.go:19-35: sort.Search, then the equality test)
+ * over the table's resident keys: d_entry[i] = index of the entry whose key equals query i, or ~0. With a
+ * filter (sstable_reader.go:49-65), a query the filter rejects stores ~0 without touching the index; NULL =
+ * no gate (Get does not consult the filter, :67-77). Of the view only index, key_off, key_len, n and
+ * index_bytes are read. The keys are taken to be strictly ascending (the writer's order; the merge plan checks it, this call does not:
+ * on an unsorted table the answers are wrong, the accesses stay in range). */
+int rio_sst_lookup(rio_ctx* ctx, const rio_sst_view* view, const uint64_t* d_pfx, const rio_bloom_view* f,
+                   const uint8_t* d_keys, const uint64_t* d_key_off, uint64_t n, uint64_t key_bytes, uint64_t* d_entry,
+                   void* stream);
 
 /* ---- DiskKeyIndex lookups (sstables/disk_key_index.go:87-140) --------------------------------
  * Batched DiskKeyIndex.Get / Contains / IteratorStartingAt: one result per query key, each the
