@@ -39,6 +39,7 @@
 
 #include "rio_device.h"
 #include "rio_dev_util.h"
+#include "rio_launch.h"
 #include "rio_sst_keys.h"
 
 namespace rio {

@@ -1,5 +1,5 @@
 // rio_device.h — structures shared by the HIP kernels (rio_kernels.hip) and the host runtime
-// (rio_capi.cpp). Internal to librio; the public boundary is include/rio.h.
+// (rio_ctx.h and the files that include it). Internal to librio; the public boundary is include/rio.h.
 #pragma once
 #include <stdint.h>
 

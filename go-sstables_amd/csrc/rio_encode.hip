@@ -20,6 +20,7 @@
 
 #include "rio_device.h"
 #include "rio_dev_util.h"
+#include "rio_launch.h"
 
 namespace rio {
 

@@ -37,6 +37,7 @@
 #include "rio_crc64.h"
 #include "rio_device.h"
 #include "rio_dev_util.h"
+#include "rio_launch.h"
 
 namespace rio {
 

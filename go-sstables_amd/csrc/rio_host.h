@@ -1,4 +1,4 @@
-// rio_host.h — host-side helpers shared by the runtime files (rio_capi.cpp, rio_replay.cpp).
+// rio_host.h — host-side helpers shared by the runtime files (the context's files through rio_ctx.h, rio_replay.cpp).
 #pragma once
 #include <algorithm>
 #include <condition_variable>
@@ -87,7 +87,7 @@ class HostPool {
 };
 
 // Framing of a file whose bytes a host producer writes piece by piece into the context's pinned
-// staging (rio_capi.cpp): fill(user, dst, off, n) writes file bytes [off, off + n) to dst and
+// staging (rio_decode.cpp): fill(user, dst, off, n) writes file bytes [off, off + n) to dst and
 // returns RIO_OK or an error, which aborts the frame. Producing piece k+1 overlaps the DMA of
 // piece k; then rio_frame's device work. Used by rio_replay.cpp (pread straight into staging, and
 // the windows of rio_stream: a synthetic file header followed by a byte range of the file).

@@ -26,6 +26,7 @@
 
 #include "rio_device.h"
 #include "rio_dev_util.h"
+#include "rio_launch.h"
 #include "rio_pb.h"
 
 namespace rio {
@@ -2382,7 +2383,7 @@ hipError_t launch_index_search_view(const uint8_t* out, const uint64_t* out_off,
 }
 
 // ------------------------------------------------------------------------------------------
-// Host-side launchers (called by rio_capi.cpp)
+// Host-side launchers (declared in rio_launch.h, called by the host runtime)
 // ------------------------------------------------------------------------------------------
 static inline unsigned blocks_for(uint64_t n, unsigned bs) {
     uint64_t b = (n + bs - 1) / bs;
@@ -2442,13 +2443,6 @@ hipError_t launch_phase_a(const FrameParams& P, hipStream_t s, hipEvent_t* ev) {
     hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, s, P);
     return hipGetLastError();
 }
-
-hipError_t launch_snappy_decode(const FrameParams& P, hipStream_t s, bool main);  // rio_snappy.hip
-hipError_t launch_snappy_batch(const FrameBatch& B, hipStream_t s);             // rio_snappy.hip
-hipError_t launch_gzip_decode(const FrameParams& P, hipStream_t s);              // rio_gzip.hip
-hipError_t launch_gzip_resize(const FrameParams& P, hipStream_t s);              // rio_gzip.hip
-hipError_t launch_lzw_decode(const FrameParams& P, hipStream_t s);               // rio_lzw.hip
-hipError_t launch_lzw_resize(const FrameParams& P, hipStream_t s);               // rio_lzw.hip
 
 // gzip redo round: records holding several members (Go's multistream reader) are sized by
 // k_gz_resize; then the scan, placement and gzip decoders run again with the corrected sizes. Every

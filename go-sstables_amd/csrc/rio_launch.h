@@ -1,0 +1,78 @@
+// rio_launch.h — every host-callable function a .hip file defines, declared once. Included by the .hip file
+// that defines each function and by every caller, so the compiler checks the two sides against each other.
+// Internal to librio.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "rio_device.h"
+
+namespace rio {
+
+// rio_kernels.hip: framing, placement and the decoders' driver
+hipError_t launch_phase_a(const FrameParams& P, hipStream_t s, hipEvent_t* ev);
+hipError_t launch_frame(const FrameParams& P, hipStream_t s, hipEvent_t* ev);
+hipError_t launch_frame_ev(const FrameParams& P, hipStream_t s, hipEvent_t walk_start, hipEvent_t walk_stop,
+                           hipEvent_t scan_stop);
+hipError_t launch_phase_b(const FrameParams& P, hipStream_t s, hipEvent_t* ev, hipEvent_t done = nullptr);
+hipError_t launch_phase_b_batch(const FrameBatch& B, hipStream_t s, hipEvent_t* ev, hipEvent_t done = nullptr);
+// rio_kernels.hip: single-record decode, the SeekNext map, DiskKeyIndex lookups
+hipError_t launch_read_at(const uint8_t* f, uint64_t len, uint64_t off, uint8_t* out, uint64_t out_cap,
+                          ReadAtResult* res, hipStream_t s);
+hipError_t launch_seek_next(const uint8_t* f, uint64_t len, uint64_t off, uint64_t seek_len, uint8_t* out,
+                            uint64_t out_cap, ReadAtResult* res, uint64_t* rec_off, hipStream_t s);
+int build_seek_map(const uint8_t* f, uint64_t len, const uint64_t* rec_off, const uint8_t* flags, uint64_t n,
+                   std::vector<uint64_t>& P, std::vector<uint64_t>& R, hipStream_t s);
+hipError_t launch_index_search(const uint8_t* f, uint64_t len, uint64_t seek_len, const uint8_t* keys,
+                               const uint64_t* key_off, uint64_t nq, const uint32_t* perm, rio_index_hit* hits,
+                               hipStream_t s);
+hipError_t launch_index_search_view(const uint8_t* out, const uint64_t* out_off, const uint8_t* flags, uint64_t n,
+                                    const uint64_t* P, uint64_t K, const uint64_t* R, uint64_t len, const uint8_t* keys,
+                                    const uint64_t* key_off, uint64_t nq, const uint32_t* perm, rio_index_hit* hits,
+                                    hipStream_t s);
+// rio_snappy.hip, rio_gzip.hip, rio_lzw.hip: the codecs (called by rio_kernels.hip)
+hipError_t launch_snappy_decode(const FrameParams& P, hipStream_t s, bool main);
+hipError_t launch_snappy_batch(const FrameBatch& B, hipStream_t s);
+hipError_t launch_gzip_decode(const FrameParams& P, hipStream_t s);
+hipError_t launch_gzip_resize(const FrameParams& P, hipStream_t s);
+hipError_t launch_lzw_decode(const FrameParams& P, hipStream_t s);
+hipError_t launch_lzw_resize(const FrameParams& P, hipStream_t s);
+// rio_sort.hip
+size_t key_sort_tmp_bytes(uint64_t n);
+hipError_t launch_key_sort(const uint8_t* keys, const uint64_t* key_off, uint64_t n, uint64_t* pfx_in, uint64_t* pfx_out,
+                           uint32_t* idx_in, uint32_t* perm, void* tmp, size_t tmp_bytes, hipStream_t s);
+// rio_sstable.hip
+hipError_t launch_sst_index(const uint8_t* arena, const uint64_t* off, uint64_t n, uint64_t* key_off,
+                            uint64_t* key_len, uint64_t* value_off, uint64_t* checksum, uint64_t* result,
+                            hipStream_t s);
+hipError_t launch_sst_validate(const uint8_t* data, const uint64_t* data_off, const uint64_t* data_rec_off,
+                               uint64_t n_data, const uint64_t* value_off, const uint64_t* checksum,
+                               uint64_t n_index, uint64_t* crc_out, uint64_t* result, hipStream_t s,
+                               const uint64_t* view = nullptr);
+hipError_t launch_sst_data_entry(const uint8_t* arena, const uint64_t* off, uint64_t n, uint64_t* view,
+                                 uint64_t* result, hipStream_t s);
+// rio_compact.hip
+size_t merge_cub_bytes(uint64_t n);
+hipError_t launch_merge_plan(const MergeParams& P, hipStream_t s);
+hipError_t launch_merge_gather(const GatherParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
+hipError_t launch_index_entries(const EntryParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
+// rio_bloom.hip
+hipError_t launch_bloom_add(const BloomParams& P, bool survivors, hipStream_t s);
+hipError_t launch_bloom_contains(const BloomParams& P, hipStream_t s);
+hipError_t launch_sst_key_prefixes(const rio_sst_view& v, uint64_t* pfx, hipStream_t s);
+hipError_t launch_sst_lookup(const BloomParams& P, const LookupParams& Q, hipStream_t s);
+// rio_flush.hip
+size_t flush_cub_bytes(uint64_t n, uint32_t max_key_len);
+hipError_t launch_flush_plan(const FlushParams& P, hipStream_t s, hipEvent_t* ev, uint32_t* n_stages);
+// rio_walops.hip
+size_t wal_cub_bytes(uint64_t n);
+hipError_t launch_wal_plan(const WalParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
+hipError_t launch_wal_gather(const WalParams& P, hipStream_t s);
+// rio_encode.hip
+hipError_t launch_encode(const EncParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
+uint64_t enc_scratch_bytes(uint64_t n, uint64_t bytes, uint32_t compression);
+uint64_t enc_table_bytes();
+size_t enc_cub_bytes(uint64_t n);
+
+}  // namespace rio

@@ -10,6 +10,8 @@
 
 #include <algorithm>
 
+#include "rio_launch.h"
+
 namespace rio {
 
 __global__ void __launch_bounds__(256) k_key_prefix(const uint8_t* keys, const uint64_t* key_off, uint64_t n,

@@ -33,6 +33,7 @@
 
 #include "rio_device.h"
 #include "rio_dev_util.h"
+#include "rio_launch.h"
 #include "rio_pb.h"
 
 namespace rio {

@@ -191,8 +191,13 @@ int rio_host_unregister(const void* p);
  * outputs of that size). A gzip file whose records of several members outgrow the framing's sizes
  * reports this only after its decode: a capacity-0 probe can undersize it, so loop on CAPACITY.
  * `stream` is a hipStream_t (NULL = the ctx stream). */
-/* Calls of one ctx share its device scratch: a device-API call on a stream other than the previous
- * call's waits (stream-ordered) for that call. Arenas grow on demand (hipMalloc); before capturing
+/* Calls of one ctx share its device scratch. The library orders the decode calls across streams:
+ * rio_device_decode, rio_device_decode_ex or rio_device_decode_batch on a stream other than the
+ * previous decode call's waits (stream-ordered) for that call, and so do rio_frame and rio_decode on
+ * the ctx stream. Every other call that takes a `stream` (rio_device_encode, rio_sst_*, rio_bloom_*,
+ * rio_wal_ops_*, rio_device_index_search) is not ordered by the library: a sequence of them on one
+ * ctx runs on one stream, and a caller that changes streams between calls sharing a ctx orders them
+ * itself (an event, or a stream wait). Arenas grow on demand (hipMalloc); before capturing
  * calls into a hipGraph, size them with rio_ctx_reserve (largest file length, record count and batch
  * size to come) so that nothing is allocated during capture, and capture on the stream of the
  * previous call. */

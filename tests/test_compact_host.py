@@ -36,7 +36,7 @@ def test_model_merge_rules():
 def test_merge_argument_errors_return_before_any_device_call():
     lib = L.lib()
     # A context cannot be created without a device, so ctx is a placeholder. It is never read: the three entry
-    # points check their arguments before the first read of *ctx (rio_capi.cpp states that order), and every
+    # points check their arguments before the first read of *ctx (rio_tables.cpp states that order), and every
     # call below is refused on its arguments. The page of zeros keeps a reordering there from reading past it.
     page = ctypes.create_string_buffer(1 << 16)
     ctx = ctypes.addressof(page)

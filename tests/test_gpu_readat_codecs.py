@@ -3,7 +3,7 @@
 mmap_reader.go:130-203 decodes any record start it is pointed at. A header that fails its CRC in the
 middle of a file ends FileReader's loop (and so the reader handle's decoded index) there, while the
 records after it stay readable by offset: the single-record kernel locates them and the host decodes
-each as a file of its own through the whole-file path (readat_expand in rio_capi.cpp). Compared with
+each as a file of its own through the whole-file path (readat_expand in rio_reader.cpp). Compared with
 the oracle's ReadNextAt / SeekNext (status, record, the failing trial's offset), payload damage after
 the break included.
 """

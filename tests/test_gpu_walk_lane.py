@@ -118,7 +118,7 @@ def test_auto_walk_follows_the_previous_decode(monkeypatch):
 
     slots = torch.cuda.get_device_properties(0).multi_processor_count * 4 * 5
 
-    def wave_cb(img):  # rio_capi.cpp wave_chunk_bytes: one round of resident walk waves, 4 KiB multiples
+    def wave_cb(img):  # rio_ctx.cpp wave_chunk_bytes: one round of resident walk waves, 4 KiB multiples
         want = ((len(img) + slots - 1) // slots + 4095) // 4096 * 4096
         return min(32768, max(want, 8192))
 
