@@ -31,6 +31,44 @@ def gpu_decode_arrays(image) -> dict:
     return res
 
 
+def decode_in_new_context(image) -> dict:
+    """Whole-file device decode in a context of its own, so it reads the environment as it is now
+    (RIO_CHUNK_BYTES under monkeypatch.setenv); arrays cut to the records delivered."""
+    import ctypes
+
+    h = ctypes.c_void_p()
+    assert L.lib().rio_ctx_create(0, ctypes.byref(h)) == 0
+    try:
+        dec = DeviceDecoder.__new__(DeviceDecoder)
+        dec.device, dec.ctx = 0, h.value
+        d_file, n = to_device_file(image)
+        b, info = dec.decode(d_file, n)
+        k = info["n_records"]
+        nb = int(b.out_off[k].item()) if info["status"] == L.RIO_ERR_UNSUPPORTED else info["total_out_bytes"]
+        return dict(info, out=b.out[:nb].cpu().numpy(), out_off=b.out_off[:k + 1].cpu().numpy(),
+                    rec_off=b.rec_off[:k].cpu().numpy(), flags=b.flags[:k].cpu().numpy())
+    finally:
+        L.lib().rio_ctx_destroy(h)
+
+
+def assert_exact_or_handed_back_at(g: dict, o: dict, redo, what=""):
+    """The result equals the oracle's; or the decode was handed back to the reference reader
+    (RIO_ERR_UNSUPPORTED) at a record known to need the redo round, everything before it exact: what
+    k_gz_resize / k_lzw_resize document for a file whose placement came from the sequential repair
+    (`st->slow`). Returns "exact" or "handed back at <index>"."""
+    if g["status"] != L.RIO_ERR_UNSUPPORTED:
+        assert_same_as_oracle(g, o, what)
+        return "exact"
+    n = g["n_records"]
+    assert n in set(redo), (what, n)
+    np.testing.assert_array_equal(g["rec_off"][:n], o["rec_off"][:n], err_msg=what)
+    np.testing.assert_array_equal(g["out_off"][:n + 1], o["out_off"][:n + 1], err_msg=what)
+    np.testing.assert_array_equal(g["flags"][:n], o["flags"][:n], err_msg=what)
+    nb = int(o["out_off"][n])
+    assert np.array_equal(g["out"][:nb], o["out"][:nb]), what
+    return f"handed back at {n}"
+
+
 def assert_same_as_oracle(g: dict, o: dict, what=""):
     assert g["status"] == o["status"], (what, g["status"], o["status"])
     assert g["n_records"] == o["n_records"], (what, g["n_records"], o["n_records"])
