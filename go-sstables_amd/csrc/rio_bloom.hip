@@ -35,27 +35,6 @@ namespace {
 
 // 256 CUs x 8 blocks of 256 lanes: longer batches go round the grid-stride loops again
 constexpr uint64_t kBloomGridCap = 2048;
-constexpr uint64_t kFnvBasis = 0xcbf29ce484222325ull, kFnvPrime = 0x100000001b3ull;
-
-typedef uint64_t __attribute__((aligned(1))) u64u;
-
-// FNV-1 (64 bit) of p[0, len); `room` >= len bytes are readable from p. Whole 8-byte unaligned loads while 8
-// bytes are readable (the last one may pass the key's end by up to 7 bytes, inside the arena: those bytes are
-// not hashed), single bytes for a tail at the arena's very end
-__device__ __forceinline__ uint64_t fnv1(const uint8_t* p, uint64_t len, uint64_t room) {
-    uint64_t h = kFnvBasis, b = 0;
-    for (; b < len && b + 8 <= room; b += 8) {
-        uint64_t w = *reinterpret_cast<const u64u*>(p + b);
-        const uint32_t cnt = (uint32_t)umin(len - b, (uint64_t)8);
-        for (uint32_t j = 0; j < cnt; j++) {
-            h = (h * kFnvPrime) ^ (w & 0xFF);
-            w >>= 8;
-        }
-    }
-    for (; b < len; b++) h = (h * kFnvPrime) ^ p[b];
-    return h;
-}
-
 // key i of an arena with offsets: clamped to [0, key_bytes); room = bytes readable from its first byte
 __device__ __forceinline__ const uint8_t* arena_key(const BloomParams& P, uint64_t i, uint64_t& len, uint64_t& room) {
     const uint64_t a = P.key_off[i], b = P.key_off[i + 1];
@@ -78,15 +57,6 @@ __device__ __forceinline__ void filter_add(const rio_bloom_view& f, const uint64
         const uint64_t idx = (h ^ s_hk[j]) % f.m;  // < m: dword idx >> 5 lies inside 8 * ceil(m / 64) bytes
         atomicOr(&words[idx >> 5], 1u << (idx & 31));
     }
-}
-
-__device__ __forceinline__ bool filter_contains(const rio_bloom_view& f, const uint64_t* s_hk, uint64_t h) {
-    const uint32_t k = umin(f.k, RIO_BLOOM_MAX_K);
-    for (uint32_t j = 0; j < k; j++) {
-        const uint64_t idx = (h ^ s_hk[j]) % f.m;
-        if (!((f.bits[idx >> 6] >> (idx & 63)) & 1)) return false;
-    }
-    return true;
 }
 
 }  // namespace

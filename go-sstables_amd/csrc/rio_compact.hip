@@ -46,16 +46,6 @@ namespace rio {
 
 namespace {
 
-constexpr uint64_t kLongValue = 1024;  // values from this length on are copied by a whole wave
-
-// value i of a view: [b, e) clamped to the data arena
-__device__ __forceinline__ bool value_at(const rio_sst_view& v, uint64_t i, uint64_t& b, uint64_t& e) {
-    const uint64_t o0 = v.data_off[i], o1 = v.data_off[i + 1];
-    b = umin(o0, v.data_bytes);
-    e = umin(umax(o1, b), v.data_bytes);
-    return b == o0 && e == o1;
-}
-
 // table of input entry number g: the last t with base[t] <= g (base in LDS, base[T] = N > g)
 __device__ __forceinline__ uint32_t table_of(const uint64_t* base, uint32_t T, uint64_t g) {
     uint32_t lo = 0, hi = T;
@@ -228,7 +218,8 @@ __global__ void __launch_bounds__(256) k_gather_copy(GatherParams P) {
         const uint8_t* s = v->data + vb;
         uint8_t* d = P.values + d0;
         // bytes up to the destination's next 16-byte boundary (the arena base is 16-byte aligned or
-        // not: the address decides), whole aligned 16-byte words, then the tail
+        // not: the address decides), whole aligned 16-byte words, then the tail. The same text as copy_item
+        // (rio_dev_util.h), kept in line here: the call compiles this kernel to other code (two more VGPRs)
         const uint64_t head = umin((uint64_t)((16 - (reinterpret_cast<uintptr_t>(d) & 15)) & 15), len);
         if (lane < head) d[lane] = s[lane];
         const uint64_t body = (len - head) & ~15ull;

@@ -290,6 +290,40 @@ struct LookupParams {
     uint64_t* entry;              // [n] entry index or ~0
 };
 
+// rio_stack.hip: a stack of loaded tables (rio_sst_stack_*). The four tables live in device memory the stack
+// owns; every kernel reads them at wave-uniform addresses
+struct StackParams {
+    const rio_sst_view* views;          // [T]
+    const uint64_t* const* pfx;         // [T] rio_sst_key_prefixes of table t
+    const rio_bloom_view* filters;      // [T] bits == null: table t has no filter
+    const uint64_t* const* stored;      // [T] the index entries' stored checksums, or null
+    uint32_t T;
+    uint32_t flag;                      // lookup: gated; value plan: check_crc; bounds: upper
+    // queries of an arena (lookup, bounds)
+    const uint8_t* keys;
+    const uint64_t* key_off;            // [n + 1]
+    uint64_t n;
+    uint64_t key_bytes;
+    uint64_t* src;                      // [n] lookup's output, the value calls' input
+    uint8_t* status;                    // [n] RIO_GET_*
+    uint64_t* tmp;                      // [n + 1] scan input (stack scratch)
+    uint64_t* val_off;                  // [n + 1]
+    uint8_t* values;
+    uint64_t values_cap;
+    uint64_t* pos;                      // [n * T] bounds
+};
+// rio_sst_keys_gather: keys of a plan's survivors
+struct KeysParams {
+    const rio_sst_view* views;
+    uint32_t T;
+    uint64_t n_out;
+    const uint64_t* out_src;            // [n_out]
+    uint64_t* tmp;                      // [n_out + 1] scan input
+    uint8_t* keys;
+    uint64_t keys_cap;
+    uint64_t* key_off;                  // [n_out + 1]
+};
+
 // protobuf varint length, and proto.Marshal's size of an IndexEntry {key = 1, valueOffset = 2, checksum = 3}:
 // proto3 omits an empty key and zero scalars (sstables/proto/sstable.proto:5-9)
 #ifdef __HIPCC__

@@ -62,6 +62,13 @@ hipError_t launch_bloom_add(const BloomParams& P, bool survivors, hipStream_t s)
 hipError_t launch_bloom_contains(const BloomParams& P, hipStream_t s);
 hipError_t launch_sst_key_prefixes(const rio_sst_view& v, uint64_t* pfx, hipStream_t s);
 hipError_t launch_sst_lookup(const BloomParams& P, const LookupParams& Q, hipStream_t s);
+// rio_stack.hip
+size_t stack_cub_bytes(uint64_t n);
+hipError_t launch_stack_lookup(const StackParams& P, hipStream_t s);
+hipError_t launch_stack_value_plan(const StackParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
+hipError_t launch_stack_value_copy(const StackParams& P, hipStream_t s);
+hipError_t launch_stack_bounds(const StackParams& P, hipStream_t s);
+hipError_t launch_keys_gather(const KeysParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
 // rio_flush.hip
 size_t flush_cub_bytes(uint64_t n, uint32_t max_key_len);
 hipError_t launch_flush_plan(const FlushParams& P, hipStream_t s, hipEvent_t* ev, uint32_t* n_stages);

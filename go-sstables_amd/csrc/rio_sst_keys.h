@@ -1,6 +1,7 @@
-// rio_sst_keys.h — keys of a loaded table on the device (rio_sst_view): the clamped accessors, the 8-byte
-// big-endian key prefix, bytes.Compare and the prefix-probed binary search. Shared by the merge plan
-// (rio_compact.hip) and the point lookup (rio_bloom.hip). Internal to librio.
+// rio_sst_keys.h — keys and values of a loaded table on the device (rio_sst_view): the clamped accessors, the
+// 8-byte big-endian key prefix, bytes.Compare and the prefix-probed binary search, and a key's FNV-1 hash with
+// the filter test on it. Shared by the merge plan (rio_compact.hip), the point lookup (rio_bloom.hip) and the
+// stack of tables (rio_stack.hip). Internal to librio.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,6 +12,16 @@
 namespace rio {
 
 constexpr uint64_t kEntryMask = (1ull << RIO_MERGE_ENTRY_BITS) - 1;
+
+constexpr uint64_t kLongValue = 1024;  // values from this length on are copied by a whole wave
+
+// value i of a view: [b, e) clamped to the data arena
+__device__ __forceinline__ bool value_at(const rio_sst_view& v, uint64_t i, uint64_t& b, uint64_t& e) {
+    const uint64_t o0 = v.data_off[i], o1 = v.data_off[i + 1];
+    b = umin(o0, v.data_bytes);
+    e = umin(umax(o1, b), v.data_bytes);
+    return b == o0 && e == o1;
+}
 
 struct Key {
     const uint8_t* p;
@@ -75,6 +86,37 @@ __device__ __forceinline__ bool entry_of(const rio_sst_view* views, uint32_t T, 
     if (t >= T || i >= v->n) {
         i = 0;
         return false;
+    }
+    return true;
+}
+
+constexpr uint64_t kFnvBasis = 0xcbf29ce484222325ull, kFnvPrime = 0x100000001b3ull;
+
+typedef uint64_t __attribute__((aligned(1))) u64u;
+
+// FNV-1 (64 bit) of p[0, len); `room` >= len bytes are readable from p. Whole 8-byte unaligned loads while 8
+// bytes are readable (the last one may pass the key's end by up to 7 bytes, inside the arena: those bytes are
+// not hashed), single bytes for a tail at the arena's very end
+__device__ __forceinline__ uint64_t fnv1(const uint8_t* p, uint64_t len, uint64_t room) {
+    uint64_t h = kFnvBasis, b = 0;
+    for (; b < len && b + 8 <= room; b += 8) {
+        uint64_t w = *reinterpret_cast<const u64u*>(p + b);
+        const uint32_t cnt = (uint32_t)umin(len - b, (uint64_t)8);
+        for (uint32_t j = 0; j < cnt; j++) {
+            h = (h * kFnvPrime) ^ (w & 0xFF);
+            w >>= 8;
+        }
+    }
+    for (; b < len; b++) h = (h * kFnvPrime) ^ p[b];
+    return h;
+}
+
+// all k probes of hash h set in filter f; hk holds the filter's min(k, RIO_BLOOM_MAX_K) hash keys (LDS or global)
+__device__ __forceinline__ bool filter_contains(const rio_bloom_view& f, const uint64_t* hk, uint64_t h) {
+    const uint32_t k = umin(f.k, RIO_BLOOM_MAX_K);
+    for (uint32_t j = 0; j < k; j++) {
+        const uint64_t idx = (h ^ hk[j]) % f.m;
+        if (!((f.bits[idx >> 6] >> (idx & 63)) & 1)) return false;
     }
     return true;
 }

@@ -214,16 +214,7 @@ __device__ __forceinline__ void wal_items(const WalParams& P, uint64_t g, WalIte
 template <uint32_t G>
 __device__ __forceinline__ void wal_copy_item(const WalItem& it, uint32_t lane) {
     if (!it.len) return;
-    const uint8_t* s = it.s;
-    uint8_t* d = it.d;
-    const uint64_t len = it.len;
-    const uint64_t head = umin((uint64_t)((16 - (reinterpret_cast<uintptr_t>(d) & 15)) & 15), len);
-    if (lane < head) d[lane] = s[lane];
-    const uint64_t body = (len - head) & ~15ull;
-    for (uint64_t k = head + 16ull * lane; k < head + body; k += 16ull * G)
-        *reinterpret_cast<uint4*>(d + k) = ldu16(s + k);
-    const uint64_t t0 = head + body;
-    if (t0 + lane < len && lane < 16) d[t0 + lane] = s[t0 + lane];
+    copy_item<G>(it.d, it.s, it.len, lane);
 }
 
 // G lanes per record, two records per round so that one's bookkeeping loads overlap the other's copy

@@ -127,6 +127,8 @@ class BloomView(ctypes.Structure):
     ]
 
 
+RIO_GET_VALUE, RIO_GET_NOT_FOUND, RIO_GET_NIL, RIO_GET_HOST = 0, 1, 2, 3  # rio_sst_stack_value_plan's status bytes
+
 RIO_FLUSH_WITH_TOMBSTONES, RIO_FLUSH_SKIP_TOMBSTONES = 0, 1
 RIO_FLUSH_MAX_KEY_LEN = 1024
 
@@ -299,6 +301,14 @@ _SIGS = {
     "rio_sst_key_prefixes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "rio_sst_lookup": (
         c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p]),
+    "rio_sst_stack_create": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_uint64, POINTER(c_void_p), c_void_p]),
+    "rio_sst_stack_free": (None, [c_void_p]),
+    "rio_sst_stack_lookup": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p]),
+    "rio_sst_stack_value_plan": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p]),
+    "rio_sst_stack_value_copy": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p]),
+    "rio_sst_stack_bounds": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_uint32, c_void_p, c_void_p]),
+    "rio_sst_keys_gather": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p]),
     "rio_sst_flush_plan": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rio_sst_flush_stage_ms": (c_int, [c_void_p, POINTER(c_float), c_int]),
     "rio_wal_ops_plan": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),

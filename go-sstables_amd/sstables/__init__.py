@@ -498,3 +498,4 @@ def NewSSTableReader(*options):  # noqa: N802
 
 from .merger import (NewSSTableMerger, ScanReduceLatestWins, ScanReduceLatestWinsSkipTombstones,  # noqa: E402,F401
                      SSTableMerger)
+from .super_reader import BytesComparator, NewSuperSSTableReader, SuperSSTableReader  # noqa: E402,F401

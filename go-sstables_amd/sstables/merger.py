@@ -201,6 +201,33 @@ def write_table_files(path: str, c: Compaction, min_key: bytes, max_key: bytes):
             raise err
 
 
+def refuse_inputs(readers):
+    """The UnsupportedError with which the device merge hands `readers` back to the reference merger, or None.
+    Shared by the merger and by SuperSSTableReader's scans, which are merges of the stack's tables."""
+    from . import SSTableReader, UnsupportedError
+
+    if not readers or len(readers) > L.RIO_MERGE_MAX_TABLES:
+        return UnsupportedError(f"merge of {len(readers)} tables (1 .. {L.RIO_MERGE_MAX_TABLES})")
+    for r in readers:
+        if not isinstance(r, SSTableReader) or r.t is None:
+            return UnsupportedError("merge inputs are open SSTableReaders of NewSSTableReader")
+        if r.meta.version == 0 or r.t.v0:
+            return UnsupportedError(f"sstable '{r.opts.basePath}': v0 tables are merged by the reference merger")
+        if r.opts.device != readers[0].opts.device:
+            return UnsupportedError("merge inputs are on different devices")
+        t = r.t
+        if t.n_index > t.n_data or t.value_bad != _NONE:
+            return UnsupportedError(f"sstable '{r.opts.basePath}': a value of the table cannot be read")
+        # a value that fails its stored checksum (a reader opened with SkipHashCheckOnLoad): with hash checks on
+        # reads the reference's scan reports it (sstable_iterator.go:100-108), so the table goes back to the
+        # reference merger; without them the value is merged as the reference merges it, and the new index
+        # carries the CRC-64 of the value as read (what WriteNext computes, sstable_writer.go:120-124)
+        if t.bad_crc != _NONE and not r.opts.skipHashCheckOnRead:
+            return UnsupportedError(f"sstable '{r.opts.basePath}': a value fails its checksum and hash checks "
+                                    "on reads are enabled")
+    return None
+
+
 class SSTableMerger:
     def __init__(self, comp=None, data_compression: int = L.COMP_SNAPPY):
         """comp: bytes comparator only (skiplist.BytesComparator, the reference's default)."""
@@ -227,7 +254,7 @@ class SSTableMerger:
     def _run(self, readers, path, mode, comp, writer_options=()):
         import torch
 
-        from . import SSTableReader, UnsupportedError, _WriterOpts, writer_filter
+        from . import UnsupportedError, _WriterOpts, writer_filter
 
         o = _WriterOpts(basePath=path)
         for f in writer_options:
@@ -240,25 +267,9 @@ class SSTableMerger:
         if comp not in (L.COMP_NONE, L.COMP_SNAPPY):
             return UnsupportedError(f"output data compression {comp}: the device encodes none and snappy")
         readers = list(readers)
-        if not readers or len(readers) > L.RIO_MERGE_MAX_TABLES:
-            return UnsupportedError(f"merge of {len(readers)} tables (1 .. {L.RIO_MERGE_MAX_TABLES})")
-        for r in readers:
-            if not isinstance(r, SSTableReader) or r.t is None:
-                return UnsupportedError("merge inputs are open SSTableReaders of NewSSTableReader")
-            if r.meta.version == 0 or r.t.v0:
-                return UnsupportedError(f"sstable '{r.opts.basePath}': v0 tables are merged by the reference merger")
-            if r.opts.device != readers[0].opts.device:
-                return UnsupportedError("merge inputs are on different devices")
-            t = r.t
-            if t.n_index > t.n_data or t.value_bad != _NONE:
-                return UnsupportedError(f"sstable '{r.opts.basePath}': a value of the table cannot be read")
-            # a value that fails its stored checksum (a reader opened with SkipHashCheckOnLoad): with hash checks on
-            # reads the reference's scan reports it (sstable_iterator.go:100-108), so the table goes back to the
-            # reference merger; without them the value is merged as the reference merges it, and the new index
-            # carries the CRC-64 of the value as read (what WriteNext computes, sstable_writer.go:120-124)
-            if t.bad_crc != _NONE and not r.opts.skipHashCheckOnRead:
-                return UnsupportedError(f"sstable '{r.opts.basePath}': a value fails its checksum and hash checks "
-                                        "on reads are enabled")
+        err = refuse_inputs(readers)
+        if err is not None:
+            return err
         device = readers[0].opts.device
         views = (L.SstView * len(readers))(*[table_view(r.t) for r in readers])
         with torch.cuda.device(device):

@@ -28,6 +28,8 @@
  *     (rio_bloom_optimal, rio_bloom_add, rio_sst_bloom_add)
  *   SSTableReader.Contains / Get, SliceKeyIndex.Get in batches    sstables/sstable_reader.go:49-77,
  *     (rio_bloom_contains, rio_sst_key_prefixes, rio_sst_lookup)  sstables/slice_key_index.go:19-35
+ *   SuperSSTableReader.Contains / Get / Scan* over a stack        sstables/super_sstable_reader.go:18-105
+ *     (rio_sst_stack_*, rio_sst_keys_gather)
  *   FileWriter.Write + fillRecordHeaderV4 (input generator only)  recordio/file_writer.go:160-233
  */
 #ifndef RIO_H
@@ -590,6 +592,69 @@ int rio_sst_key_prefixes(rio_ctx* ctx, const rio_sst_view* view, uint64_t* d_pfx
 int rio_sst_lookup(rio_ctx* ctx, const rio_sst_view* view, const uint64_t* d_pfx, const rio_bloom_view* f,
                    const uint8_t* d_keys, const uint64_t* d_key_off, uint64_t n, uint64_t key_bytes, uint64_t* d_entry,
                    void* stream);
+
+/* ---- a stack of loaded tables: SuperSSTableReader on the device (rio_stack.hip) ----------------
+ * Replaces SuperSSTableReader.Contains / Get (sstables/super_sstable_reader.go:18-49: the readers from newest
+ * to oldest, the first table that holds the key answers) for a batch of query keys, and gives the cut points of
+ * ScanStartingAt / ScanRange (slice_key_index.go:49-70) for every table of the stack; the scans themselves are
+ * rio_sst_merge_plan(RIO_MERGE_LATEST_WINS) over the cut views, rio_sst_merge_gather and rio_sst_keys_gather.
+ * Table t of a stack is views[t]; position is age, the highest is the newest, as for rio_sst_merge_plan.
+ *
+ * rio_sst_stack_create copies the views, the prefix pointers (rio_sst_key_prefixes of every table), the filters
+ * (bits == NULL: that table has no filter; filters == NULL: no table has one) and the stored-checksum pointers
+ * (the index entries' Checksum arrays, rio_sst_index_parse's d_checksum; an entry or the array may be NULL) to
+ * device memory the stack owns, and sizes all scratch for batches of up to max_batch queries (8 bytes per
+ * query and the scan's temp). It waits for that one copy. After create no stack call allocates, synchronises
+ * with the host or reads a host array: every stack call can be captured into a hipGraph. The tables' arrays
+ * must stay valid while the stack is used. Stack calls are stream-ordered (NULL = the stream of the context
+ * the stack was created on).
+ * RIO_ERR_ARG before any device call and before *ctx is read: a NULL ctx / views / d_pfx / out, T = 0,
+ * T > RIO_MERGE_MAX_TABLES, max_batch = 0, a table with n > 0 and a NULL array or prefix pointer, a filter
+ * (bits != NULL) with k = 0, k > RIO_BLOOM_MAX_K, m < 2 or NULL hash keys. RIO_ERR_UNSUPPORTED for a table of
+ * 2^40 entries and more or max_batch >= 2^31 - 1.
+ * Every table and entry number read back from a buffer is clamped to what exists, every range to its arena,
+ * every store is checked against its capacity: a wrong d_src gives ~0, RIO_GET_NOT_FOUND or wrong bytes, never
+ * an out-of-range access. */
+typedef struct rio_sst_stack rio_sst_stack;
+#define RIO_GET_VALUE 0u     /* the value's bytes are at d_val_off[i] (an empty value has length 0) */
+#define RIO_GET_NOT_FOUND 1u /* no table holds the key (d_src[i] = ~0, or a word that names no entry) */
+#define RIO_GET_NIL 2u       /* the newest entry's record is nil: Get returns nil without an error and does not
+                                fall through to an older table */
+#define RIO_GET_HOST 3u      /* the host produces the reader's error: the data record does not decompress
+                                (RIO_FLAG_CORRUPT / RIO_FLAG_EOF), or the value fails its stored checksum */
+int rio_sst_stack_create(rio_ctx* ctx, const rio_sst_view* views, const uint64_t* const* d_pfx,
+                         const rio_bloom_view* filters, const uint64_t* const* d_stored_checksum, uint32_t n_tables,
+                         uint64_t max_batch, rio_sst_stack** out, void* stream);
+void rio_sst_stack_free(rio_sst_stack* stack); /* NULL is accepted */
+/* d_src[i] = table << RIO_MERGE_ENTRY_BITS | entry of the newest table whose keys contain query i =
+ * d_keys[d_key_off[i] .. d_key_off[i + 1]), or ~0. gated = 1 is Contains: a table whose filter rejects the key
+ * is skipped without touching its index (sstable_reader.go:49-65), tables without a filter are searched.
+ * gated = 0 is Get, which never asks a filter (:67-77). key_bytes is the arena's length; nothing past it is
+ * read. n > max_batch is RIO_ERR_ARG, n = 0 a no-op. */
+int rio_sst_stack_lookup(rio_sst_stack* stack, uint32_t gated, const uint8_t* d_keys, const uint64_t* d_key_off,
+                         uint64_t n, uint64_t key_bytes, uint64_t* d_src, void* stream);
+/* Per query a status byte (RIO_GET_*) and d_val_off[n + 1], the exclusive scan of the value lengths
+ * (RIO_GET_VALUE: the value's length; the others 0). The host reads d_val_off[n] to size the value arena: the
+ * sequence's one round trip. check_crc != 0 is EnableHashCheckOnReads: RIO_GET_HOST when the table has stored
+ * checksums, the entry's is not 0 and differs from the view's crc (sstable_reader.go:99-114). */
+int rio_sst_stack_value_plan(rio_sst_stack* stack, const uint64_t* d_src, uint64_t n, uint32_t check_crc,
+                             uint8_t* d_status, uint64_t* d_val_off, void* stream);
+/* The values back to back in query order: value i to d_values[d_val_off[i] .. d_val_off[i + 1]). A value that
+ * would pass values_cap is not copied. */
+int rio_sst_stack_value_copy(rio_sst_stack* stack, const uint64_t* d_src, uint64_t n, const uint64_t* d_val_off,
+                             uint8_t* d_values, uint64_t values_cap, void* stream);
+/* d_pos[k * T + t] = lower bound (upper = 0: entries of table t before the first key >= key k) or upper bound
+ * (upper = 1: entries up to the last key <= key k) of key k in table t: where IteratorStartingAt starts and
+ * IteratorBetween starts and ends (both ends inclusive). */
+int rio_sst_stack_bounds(rio_sst_stack* stack, const uint8_t* d_keys, const uint64_t* d_key_off, uint64_t n_keys,
+                         uint64_t key_bytes, uint32_t upper, uint64_t* d_pos, void* stream);
+/* The keys of the last plan's survivors (rio_sst_merge_plan or rio_sst_flush_plan on this context), laid out as
+ * rio_sst_merge_gather lays out their values: d_key_off[n_out + 1] is the scan of the key lengths, key j =
+ * d_keys[d_key_off[j] .. d_key_off[j + 1]). A key that would pass keys_cap is not copied (the plan's
+ * RIO_MERGE_R_KEY_BYTES sizes it). RIO_ERR_STATE without a plan, RIO_ERR_ARG for n_out above the plan's entry
+ * count. Allocates nothing. */
+int rio_sst_keys_gather(rio_ctx* ctx, const uint64_t* d_out_src, uint64_t n_out, uint8_t* d_keys, uint64_t keys_cap,
+                        uint64_t* d_key_off, void* stream);
 
 /* ---- DiskKeyIndex lookups (sstables/disk_key_index.go:87-140) --------------------------------
  * Batched DiskKeyIndex.Get / Contains / IteratorStartingAt: one result per query key, each the
