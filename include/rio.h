@@ -251,7 +251,10 @@ int rio_ctx_set_timing(rio_ctx* ctx, int enable);
  * the value is the data record whose file offset is valueOffset (getValueAtOffset, :85-92), its
  * CRC-64/ISO (checksumValue, :240-248) goes to d_crc_out[i]. d_result[0] = first entry whose
  * non-zero checksum mismatches (ChecksumError), d_result[1] = first entry not in the writer's
- * layout (valueOffset != data record i's offset: keep the reference reader); ~0 = none. */
+ * layout (valueOffset != data record i's offset: keep the reference reader); ~0 = none. An entry
+ * outside the layout whose valueOffset is another data record's offset gets that record's CRC-64, and
+ * its checksum is compared with it; one whose valueOffset is no data record's offset (every entry when
+ * n_data == 0) gets d_crc_out[i] = 0 and no checksum comparison. */
 int rio_sst_index_parse(rio_ctx* ctx, const uint8_t* d_index_out, const uint64_t* d_index_off, uint64_t n,
                         uint64_t* d_key_off, uint64_t* d_key_len, uint64_t* d_value_off, uint64_t* d_checksum,
                         uint64_t* d_result, void* stream);
