@@ -213,6 +213,12 @@ struct rio_ctx {
         bool planned = false;
     } wal;
 
+    // rio_wal_ops_encode (rio_tables.cpp): the scan input (n + 1 words) and the 4 meta words in one allocation,
+    // scan temp; grow-only, so a call with no more ops than an earlier one allocates nothing
+    struct WalEnc {
+        rio::DevBuf scr, cub;
+    } walenc;
+
     // the two pinned staging pieces of h2d_staged / d2h_staged / h2d_fill and the event behind each piece's DMA
     struct Staging {
         uint8_t* pinned[2] = {nullptr, nullptr};

@@ -270,6 +270,17 @@ struct WalParams {
     uint64_t* op_rec;             // [n_ops] or null
 };
 
+// rio_walenc.hip: an op log to WalMutation records (rio_wal_ops_encode)
+struct WalEncParams {
+    rio_ops_view ops;             // by value: nothing is copied to the device beforehand
+    uint8_t* records;             // record arena
+    uint64_t records_cap;
+    uint64_t* rec_off;            // [n + 1] the caller's: exclusive scan of len
+    uint64_t* len;                // [n + 1] scan input (context scratch): record lengths, item n = 0
+    uint64_t* meta;               // [4] smallest (bad op << 3 | class), longest key, upserts, deletes
+    uint64_t* result;             // [RIO_WALENC_RESULT_WORDS]
+};
+
 // rio_bloom.hip: bloom filter build / query and the point lookup of a loaded table (rio_bloom_*, rio_sst_lookup)
 struct BloomParams {
     rio_bloom_view f;             // the filter (bits == null: rio_sst_lookup without a gate)

@@ -76,6 +76,9 @@ hipError_t launch_flush_plan(const FlushParams& P, hipStream_t s, hipEvent_t* ev
 size_t wal_cub_bytes(uint64_t n);
 hipError_t launch_wal_plan(const WalParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
 hipError_t launch_wal_gather(const WalParams& P, hipStream_t s);
+// rio_walenc.hip
+size_t walenc_cub_bytes(uint64_t n);
+hipError_t launch_walenc(const WalEncParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
 // rio_encode.hip
 hipError_t launch_encode(const EncParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
 uint64_t enc_scratch_bytes(uint64_t n, uint64_t bytes, uint32_t compression);

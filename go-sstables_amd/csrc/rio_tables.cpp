@@ -421,6 +421,36 @@ extern "C" int rio_wal_ops_gather(rio_ctx* ctx, uint64_t n_ops, uint8_t* d_keys,
 }
 
 // ------------------------------------------------------------------------------------------
+// batched writes: an op log to WalMutation records (rio_walenc.hip)
+// ------------------------------------------------------------------------------------------
+extern "C" uint64_t rio_wal_ops_encode_bound(uint64_t n, uint64_t key_bytes, uint64_t value_bytes) {
+    // per record: the member's, the key's and the value's tag, and three varints of at most 10 bytes
+    return key_bytes + value_bytes + 33 * n;
+}
+
+extern "C" int rio_wal_ops_encode(rio_ctx* ctx, const rio_ops_view* ops, uint8_t* d_records, uint64_t records_cap,
+                                  uint64_t* d_rec_off, uint64_t* d_result, void* stream) {
+    if (!ctx || !ops || !d_rec_off || !d_result || (records_cap && !d_records)) return RIO_ERR_ARG;
+    const uint64_t n = ops->n;
+    if (n && (!ops->keys || !ops->key_off || !ops->values || !ops->val_off || !ops->flags)) return RIO_ERR_ARG;
+    if (n >= (1ull << 31) - 1) return RIO_ERR_UNSUPPORTED;
+    // from here on *ctx is read
+    HIP_TRY(hipSetDevice(ctx->device));
+    rio_ctx::WalEnc& W = ctx->walenc;
+    HIP_TRY(W.scr.ensure((n + 1 + 4) * 8));
+    HIP_TRY(W.cub.ensure(std::max<size_t>(walenc_cub_bytes(n), 256)));
+    WalEncParams P{};
+    P.ops = *ops;
+    P.records = d_records;
+    P.records_cap = records_cap;
+    P.rec_off = d_rec_off;
+    P.meta = W.scr.as<uint64_t>();  // the meta words first: their place does not move with n
+    P.len = P.meta + 4;
+    P.result = d_result;
+    return hip_status(launch_walenc(P, W.cub.p, W.cub.cap, stream_of(ctx, stream)));
+}
+
+// ------------------------------------------------------------------------------------------
 // sstables: host-memory table handle (the cgo NewSSTableReader binding)
 // ------------------------------------------------------------------------------------------
 struct rio_sst {

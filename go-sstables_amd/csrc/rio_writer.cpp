@@ -370,6 +370,14 @@ extern "C" int rio_writer_write(rio_writer* w, const uint8_t* record, uint64_t l
 
 extern "C" uint64_t rio_writer_size(rio_writer* w) { return w ? w->offset : 0; }
 
+extern "C" int rio_writer_append_framed(rio_writer* w, const uint8_t* bytes, uint64_t len) {
+    if (!w || !w->f) return RIO_ERR_STATE;
+    if (len && !bytes) return RIO_ERR_ARG;
+    if (len && fwrite(bytes, 1, len, w->f) != len) return RIO_ERR_IO;
+    w->offset += len;
+    return RIO_OK;
+}
+
 extern "C" int rio_writer_close(rio_writer* w) {
     if (!w) return RIO_ERR_ARG;
     int rc = RIO_OK;

@@ -61,6 +61,35 @@ def flush_ops_on_device(ctx, device: int, ops_view, mode: int, comp: int, mark=N
     return on_device_stream(device, run)
 
 
+class DeviceOps:
+    """An op log in device memory: the tensors (kept alive here) and the OpsView over them."""
+
+    def __init__(self, device: int, keys, key_off, values, val_off, flags, n: int, key_bytes: int, value_bytes: int,
+                 max_key_len: int):
+        self.device, self.n, self.max_key_len = device, n, max_key_len
+        self.keys, self.key_off, self.values, self.val_off, self.flags = keys, key_off, values, val_off, flags
+        self.view = L.OpsView(keys=keys.data_ptr(), key_off=key_off.data_ptr(), values=values.data_ptr(),
+                              val_off=val_off.data_ptr(), flags=flags.data_ptr(), n=n, key_bytes=key_bytes,
+                              value_bytes=value_bytes)
+
+
+def upload_ops(device: int, keys: bytearray, key_off, values: bytearray, val_off, flags: bytearray,
+               max_key_len: int) -> DeviceOps:
+    """The host arrays of an op log (MemStore's, simpledb.WriteBatch's) to device `device`, with the pad
+    bytes rio_ops_view asks for past each arena. Call under torch.cuda.device(device)."""
+    import numpy as np
+    import torch
+
+    dev = f"cuda:{device}"
+    up = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+    pad = bytearray(L.RIO_DEVICE_PAD)
+    return DeviceOps(device,
+                     up(np.frombuffer(keys + pad, dtype=np.uint8)), up(np.asarray(key_off, dtype=np.int64)),
+                     up(np.frombuffer(values + pad, dtype=np.uint8)), up(np.asarray(val_off, dtype=np.int64)),
+                     up(np.frombuffer(flags + bytearray(1), dtype=np.uint8)), len(flags), len(keys), len(values),
+                     max_key_len)
+
+
 class _Iterator:
     """SkipListSStableIterator (memstore/sstable_iterator.go): keys ascending, nil for a tombstoned key."""
 
@@ -183,7 +212,6 @@ class MemStore:
         return bytes(self._keys[self._key_off[op]:self._key_off[op + 1]])
 
     def _flush(self, mode, writer_options):
-        import numpy as np
         import torch
 
         from sstables import UnsupportedError, _WriterOpts, writer_filter
@@ -202,20 +230,10 @@ class MemStore:
         if self._max_key_len > L.RIO_FLUSH_MAX_KEY_LEN:
             return UnsupportedError(f"a key of {self._max_key_len} bytes: the device flush orders keys of up to "
                                     f"{L.RIO_FLUSH_MAX_KEY_LEN}")
-        n = len(self._flags)
-        dev = f"cuda:{self.device}"
         with torch.cuda.device(self.device):
-            up = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
-            pad = bytearray(L.RIO_DEVICE_PAD)
-            keys = up(np.frombuffer(self._keys + pad, dtype=np.uint8))
-            values = up(np.frombuffer(self._values + pad, dtype=np.uint8))
-            key_off = up(np.asarray(self._key_off, dtype=np.int64))
-            val_off = up(np.asarray(self._val_off, dtype=np.int64))
-            flags = up(np.frombuffer(self._flags + bytearray(1), dtype=np.uint8))
-            view = L.OpsView(keys=keys.data_ptr(), key_off=key_off.data_ptr(), values=values.data_ptr(),
-                             val_off=val_off.data_ptr(), flags=flags.data_ptr(), n=n, key_bytes=len(self._keys),
-                             value_bytes=len(self._values))
-            c = flush_ops_on_device(L.default_ctx(self.device), self.device, view, mode, o.dataCompressionType,
+            ops = upload_ops(self.device, self._keys, self._key_off, self._values, self._val_off, self._flags,
+                             self._max_key_len)
+            c = flush_ops_on_device(L.default_ctx(self.device), self.device, ops.view, mode, o.dataCompressionType,
                                     max_key_len=self._max_key_len, flt=flt)
             if c.status is not None:
                 return GoError(f"memstore flush '{o.basePath}': op {c.unsorted_table} of the log was rejected")

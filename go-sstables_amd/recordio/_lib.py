@@ -153,6 +153,9 @@ RIO_WAL_RESULT_WORDS = 8
 (RIO_WAL_R_N_RECORDS, RIO_WAL_R_N_OPS, RIO_WAL_R_KEY_BYTES, RIO_WAL_R_VALUE_BYTES, RIO_WAL_R_MAX_KEY_LEN,
  RIO_WAL_R_FIRST_BAD, RIO_WAL_R_BAD_CLASS) = range(7)
 RIO_WAL_BAD_PROTO, RIO_WAL_BAD_UTF8, RIO_WAL_BAD_VALUE_NIL, RIO_WAL_BAD_RANGE = 1, 2, 3, 4
+RIO_WALENC_RESULT_WORDS = 8
+(RIO_WALENC_R_N_RECORDS, RIO_WALENC_R_BYTES, RIO_WALENC_R_N_UPSERTS, RIO_WALENC_R_N_DELETES, RIO_WALENC_R_MAX_KEY_LEN,
+ RIO_WALENC_R_FIRST_BAD, RIO_WALENC_R_BAD_CLASS) = range(7)
 
 
 class WalSegment(ctypes.Structure):
@@ -315,6 +318,9 @@ _SIGS = {
     "rio_wal_ops_gather": (
         c_int, [c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p,
                 c_void_p]),
+    "rio_wal_ops_encode_bound": (c_uint64, [c_uint64, c_uint64, c_uint64]),
+    "rio_wal_ops_encode": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p]),
+    "rio_writer_append_framed": (c_int, [c_void_p, c_void_p, c_uint64]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -33,6 +33,13 @@ class FileWriter:
                                           byref(off))
         return (off.value, None) if rc == L.RIO_OK else (0, GoError(L.strerror(rc)))
 
+    def WriteFramed(self, data):  # noqa: N802
+        """Not in the reference: appends already-framed records (a device-encoded image without its file
+        header, or a part of it cut at record boundaries) as they are; Size() grows by len(data)."""
+        buf = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8))
+        rc = L.lib().rio_writer_append_framed(self._h, buf.ctypes.data if buf.size else None, buf.size)
+        return None if rc == L.RIO_OK else GoError(L.strerror(rc))
+
     def Size(self) -> int:  # noqa: N802
         return int(L.lib().rio_writer_size(self._h))
 

@@ -5,13 +5,20 @@ reference joins its stages with one host loop: proto.Unmarshal of every WAL reco
 memStore.Upsert / Tombstone, then FlushWithTombstones. Here the decoded WAL stays in HBM: rio_wal_ops_plan /
 rio_wal_ops_gather (csrc/rio_walops.hip) turn the decoded records into the op log rio_sst_flush_plan takes, and
 the flush's back end writes the table. The host reads the plan's 64-byte result block, then what the flush
-reads. Functions return Go-style error values. There is no CPU fallback.
+reads.
+
+The write side is batched the same way: a WriteBatch holds db.PutBytes / db.DeleteBytes calls (db.go:256-347) as
+the memstore's op log, append_batch marshals every op into its WalMutation record on the device
+(rio_wal_ops_encode, csrc/rio_walenc.hip), frames the records into WAL file images (rio_device_encode) and
+writes them through wal.Appender.AppendFramed; the same device arrays then go to memstore.flush_ops_on_device.
+Functions return Go-style error values. There is no CPU fallback.
 """
 from __future__ import annotations
 
 import ctypes
 import os
 import shutil
+import types
 
 from recordio import _lib as L
 from recordio.errors import EOF, ErrUnsupported, GoError, errors_is, wrap
@@ -202,6 +209,140 @@ def recover_wal(base_path: str, table_path: str, device: int = 0, compression: i
         torch.cuda.synchronize(device)
     err = _reset_dir(base_path)
     return n_records, wrote, err
+
+
+ErrEmptyKeyValue = GoError("neither empty keys nor values are allowed")  # db.go:37
+
+
+class WriteBatch:
+    """A batch of db.PutBytes / db.DeleteBytes calls (db.go:244-347) kept as the op log MemStore keeps:
+    key arena, value arena, offsets and flags in application order. append_batch encodes it into WAL files
+    on the device and hands back the device arrays for memstore.flush_ops_on_device."""
+
+    def __init__(self):
+        self._keys, self._values = bytearray(), bytearray()
+        self._key_off, self._val_off = [0], [0]
+        self._flags = bytearray()
+        self._max_key_len = 0
+
+    def __len__(self):
+        return len(self._flags)
+
+    def _log(self, key: bytes, value):
+        self._keys += key
+        self._key_off.append(len(self._keys))
+        if value is not None:
+            self._values += value
+        self._val_off.append(len(self._values))
+        self._flags.append(L.RIO_FLAG_NIL if value is None else 0)
+        self._max_key_len = max(self._max_key_len, len(key))
+
+    def PutBytes(self, key, value):  # noqa: N802
+        """db.PutBytes (db.go:256): never refused; a nil key or value marshals as the empty one."""
+        self._log(bytes(key or b""), bytes(value or b""))
+        return None
+
+    def DeleteBytes(self, key):  # noqa: N802
+        """db.DeleteBytes (db.go:311): never refused."""
+        self._log(bytes(key or b""), None)
+        return None
+
+    def Put(self, key: str, value: str):  # noqa: N802
+        """db.Put (db.go:244)."""
+        if len(key) == 0 or len(value) == 0:
+            return ErrEmptyKeyValue
+        return self.PutBytes(key.encode(), value.encode())
+
+    def Delete(self, key: str):  # noqa: N802
+        """db.Delete (db.go:306)."""
+        return self.DeleteBytes(key.encode())
+
+    def upload(self, device: int = 0):
+        """-> memstore.DeviceOps: the batch in device memory. Call under torch.cuda.device(device)."""
+        from memstore import upload_ops
+
+        return upload_ops(device, self._keys, self._key_off, self._values, self._val_off, self._flags, self._max_key_len)
+
+
+def wal_records_on_device(ctx, device: int, ops_view, mark=None):
+    """rio_wal_ops_encode on torch's current stream: the WalMutation record of every op of `ops_view` (an
+    OpsView). Returns (records, rec_off, result): the record arena (with RIO_DEVICE_PAD bytes past the
+    bound), its n + 1 offsets and the result words as a list; reading those 64 bytes is the one host round
+    trip. `mark(name)` as for sstables.merger.compact_on_device."""
+    import torch
+
+    from sstables.merger import check_status, on_device_stream
+
+    mark = mark or (lambda name: None)
+    lib, dev = L.lib(), f"cuda:{device}"
+    n = int(ops_view.n)
+    cap = int(lib.rio_wal_ops_encode_bound(n, ops_view.key_bytes, ops_view.value_bytes))
+
+    def run(st):
+        records = torch.empty(cap + L.RIO_DEVICE_PAD, dtype=torch.uint8, device=dev)
+        rec_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        res = torch.empty(L.RIO_WALENC_RESULT_WORDS, dtype=torch.int64, device=dev)
+        check_status(lib.rio_wal_ops_encode(ctx, ctypes.addressof(ops_view), records.data_ptr(), cap, rec_off.data_ptr(),
+                                            res.data_ptr(), st), "rio_wal_ops_encode")
+        mark("wal_encode")
+        r = [x & _NONE for x in res.cpu().tolist()]
+        mark("wal_encode_result_read")
+        return records, rec_off, r
+
+    return on_device_stream(device, run)
+
+
+def append_batch(appender, batch, device: int = 0, mark=None):
+    """The WAL half of a loop of db.PutBytes / db.DeleteBytes over `batch` (a WriteBatch, or a
+    memstore.DeviceOps that is on the device already): upload, rio_wal_ops_encode, rio_device_encode with
+    the appender's writer's compression, the image and its offsets to the host, wal.Appender.AppendFramed.
+    The directory is what the host loop of proto.marshal_upsert / marshal_delete + Append leaves. Returns
+    (ops, err): ops is the memstore.DeviceOps, whose view memstore.flush_ops_on_device takes as it is."""
+    import torch
+
+    from recordio.writer import FileWriter
+    from sstables import UnsupportedError
+    from sstables.merger import check_status, on_device_stream
+
+    mark = mark or (lambda name: None)
+    w = appender.currentWriter
+    if not isinstance(w, FileWriter) or w.compression not in (L.COMP_NONE, L.COMP_SNAPPY):
+        return None, UnsupportedError("append_batch writes through a recordio.FileWriter with compression none or snappy")
+    comp = w.compression
+    lib, dev = L.lib(), f"cuda:{device}"
+    with torch.cuda.device(device):
+        ctx = L.default_ctx(device)
+        if isinstance(batch, WriteBatch):
+            ops = batch.upload(device)
+        elif isinstance(batch, L.OpsView):  # the caller keeps the arrays alive
+            ops = types.SimpleNamespace(view=batch)
+        else:
+            ops = batch
+        mark("upload")
+        n = int(ops.view.n)
+        if n == 0:
+            return ops, None
+        records, rec_off, r = wal_records_on_device(ctx, device, ops.view, mark)
+        if r[L.RIO_WALENC_R_FIRST_BAD] != _NONE:
+            return ops, GoError(f"append batch: op {r[L.RIO_WALENC_R_FIRST_BAD]} of the log was rejected")
+        total = r[L.RIO_WALENC_R_BYTES]
+        cap = int(lib.rio_encode_bound(n, total, comp))
+
+        def run(st):
+            img = torch.empty(cap, dtype=torch.uint8, device=dev)
+            out_off, out_len = torch.empty(n, dtype=torch.int64, device=dev), torch.empty(1, dtype=torch.int64, device=dev)
+            check_status(lib.rio_device_encode(ctx, records.data_ptr(), rec_off.data_ptr(), None, n, total, comp,
+                                               img.data_ptr(), cap, out_off.data_ptr(), out_len.data_ptr(), st),
+                         "rio_device_encode(wal)")
+            mark("recordio_encode")
+            flen = int(out_len.item())
+            image, offs, raw = img[:flen].cpu().numpy(), out_off.cpu().numpy(), rec_off.cpu().numpy()
+            mark("d2h")
+            return image, offs, raw
+
+        image, offs, raw = on_device_stream(device, run)
+    err = appender.AppendFramed(image, offs, raw[1:] - raw[:-1])
+    return ops, err
 
 
 def _reset_dir(base_path: str):

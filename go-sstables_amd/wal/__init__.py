@@ -10,6 +10,10 @@ loop over ReaderI exactly (replayer.go:39-74).
 The appender (appender.go), cleaner (cleaner.go) and options (write_ahead_log.go) are mirrored so
 that WAL directories can be produced and the reference's tests read the same. They are host-side
 input generators, not part of the decode path. There is no CPU decode fallback.
+
+Appender.AppendFramed takes a whole batch of records that the device has marshalled and framed already
+(simpledb.append_batch: rio_wal_ops_encode, rio_device_encode) and writes it with Append's rotation rule, which
+batch_cuts works out for the batch on the host.
 """
 from __future__ import annotations
 
@@ -235,6 +239,36 @@ def NewReplayer(opts: Options):  # noqa: N802
 # ------------------------------------------------------------------------------------------------
 # appender / cleaner (host-side generators of WAL directories)
 # ------------------------------------------------------------------------------------------------
+def batch_cuts(size0, raw_len, framed_len, max_size):
+    """Where a loop of Append rotates (checkSizeAndRotate, appender.go:72), for records that are framed
+    already: the current file holds size0 bytes; record i rotates the file first when size + raw_len[i] >
+    max_size, after which the size is 8 (the new file's header), then the size grows by framed_len[i].
+    Returns the ascending list of the records i that are the first of a new file. Every record is checked
+    once, so an oversize record leaves a header-only file behind it when it is the first of the batch in a
+    fresh file. Pure host arithmetic: the framed length can be below the raw one (Snappy), so the test is
+    not monotone in i and the walk from one cut to the next is serial; inside a file it is one numpy
+    comparison over a window that doubles until it holds the next cut."""
+    raw = np.asarray(raw_len, dtype=np.int64)
+    cum = np.concatenate([[0], np.cumsum(np.asarray(framed_len, dtype=np.int64))])
+    n = len(raw)
+    cuts = []
+    start, base = 0, int(size0)  # the next record to check, and the file's size before record `start`
+    while start < n:
+        hit, lo, width = -1, start, 1024
+        while lo < n and hit < 0:
+            hi = min(n, lo + width)
+            over = (base - int(cum[start])) + cum[lo:hi] + raw[lo:hi] > max_size
+            if over.any():
+                hit = lo + int(np.argmax(over))
+            lo, width = hi, 2 * width
+        if hit < 0:
+            break
+        cuts.append(hit)
+        # record `hit` opens the new file and is not checked again
+        start, base = hit + 1, 8 + int(cum[hit + 1] - cum[hit])
+    return cuts
+
+
 class Appender:
     """appender.go:13-120"""
 
@@ -282,6 +316,43 @@ class Appender:
         _, err = self.currentWriter.Write(record)
         if err is not None:
             return wrap(f"error while appending to sync wal writer '{self.currentWriterPath}'", err)
+        return None
+
+    def AppendFramed(self, image, out_rec_off, raw_len):  # noqa: N802
+        """Not in the reference: a loop of Append over records that are framed already. `image` is a v4 file
+        image as rio_device_encode writes it for the records (its 8-byte header is not written again),
+        out_rec_off[i] record i's offset in it and raw_len[i] the record's length before framing, which is what
+        Append checks the file size with. The records go through the current writer and Rotate() at
+        batch_cuts' indices, so a part-filled current file, nextWriterNumber and the one-million-file error
+        carry on as under Append. UnsupportedError unless the current writer is a recordio.FileWriter with
+        compression none or snappy, the image's compression."""
+        from recordio.writer import FileWriter
+        from sstables import UnsupportedError
+
+        w = self.currentWriter
+        if not isinstance(w, FileWriter) or w.compression not in (L.COMP_NONE, L.COMP_SNAPPY):
+            return UnsupportedError("AppendFramed writes through a recordio.FileWriter with compression none or snappy")
+        img = np.frombuffer(image, dtype=np.uint8)
+        off = np.asarray(out_rec_off, dtype=np.int64)
+        raw = np.asarray(raw_len, dtype=np.int64)
+        n = len(off)
+        if img.size < 8 or len(raw) != n or int.from_bytes(img[4:8].tobytes(), "little") != w.compression:
+            return UnsupportedError("AppendFramed: the image is not a v4 file of the writer's compression over these records")
+        off = np.concatenate([off, [img.size]])
+        cuts = batch_cuts(w.Size(), raw, np.diff(off), self.walOptions.maxWalFileSize)
+        a = 0
+        for b in cuts + [None]:  # records a .. b - 1 into the current file, then the rotation before record b
+            end = n if b is None else b
+            if end > a:
+                err = self.currentWriter.WriteFramed(img[off[a]:off[end]])
+                if err is not None:
+                    return wrap(f"error while appending to wal writer '{self.currentWriterPath}'", err)
+            if b is not None:
+                _, err = self.Rotate()
+                if err is not None:
+                    err = wrap(f"error rotating appender at '{self.currentWriterPath}'", err)
+                    return wrap(f"error while rotating wal writer '{self.currentWriterPath}'", err)
+            a = end
         return None
 
     def Rotate(self):  # noqa: N802

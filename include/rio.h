@@ -543,6 +543,45 @@ int rio_wal_ops_gather(rio_ctx* ctx, uint64_t n_ops, uint8_t* d_keys, uint64_t k
                        uint8_t* d_values, uint64_t values_cap, uint64_t* d_val_off, uint8_t* d_flags,
                        uint64_t* d_op_rec /* may be NULL: source record index of each op */, void* stream);
 
+/* ---- batched writes: an op log to WalMutation records on the device (rio_walenc.hip) ------------
+ * Replaces the per-mutation proto.Marshal of db.PutBytes / db.DeleteBytes (simpledb/db.go:256-347: the
+ * WalMutation of db.go:258-265 / :312-318, marshalled, appended to the WAL, applied to the memstore) for a
+ * batch kept as a rio_ops_view, the inverse of rio_wal_ops_plan / _gather. Record i is proto.Marshal's
+ * output: deterministic field order, proto3 empty fields omitted, minimal varints, the oneof member always
+ * present.
+ *   upsert (flags[i] without RIO_FLAG_NIL): 0A varint(body), then 1A varint(klen) key when klen > 0 (keyBytes =
+ *            3), then 22 varint(vlen) value when vlen > 0 (valueBytes = 4)
+ *   delete (RIO_FLAG_NIL; the value range is not read): 12 varint(body), then 12 varint(klen) key when
+ *            klen > 0 (keyBytes = 2)
+ * so an empty-key upsert with an empty value is 0A 00 and an empty-key delete 12 00. The records go to
+ * d_records back to back in the layout rio_device_encode takes (which frames them into a WAL file image,
+ * byte-identical to FileWriter.Write):
+ *   d_records [records_cap]  records_cap >= rio_wal_ops_encode_bound(n, key_bytes, value_bytes) always fits
+ *                            (+ RIO_DEVICE_PAD readable bytes for rio_device_encode)
+ *   d_rec_off [n + 1]        record i = d_records[d_rec_off[i] .. d_rec_off[i + 1])
+ *   d_result                 uint64[RIO_WALENC_RESULT_WORDS]
+ * A record whose end passes records_cap is not written; d_rec_off and d_result are complete either way.
+ * Every key and value range is checked: not monotone or leaving its arena (key_bytes / value_bytes) gives
+ * RIO_WALENC_R_FIRST_BAD = the smallest such op with class RIO_WAL_BAD_RANGE, nothing else is meaningful
+ * then and no record byte is promised; nothing is read outside a clamped range, every store is checked
+ * against records_cap. Stream-ordered (NULL = the ctx stream), no host wait; the view is passed by value
+ * into the launches. Scratch (8 bytes per op and the scan's temp) is grow-only in the context: after one
+ * call with n at least as large the call allocates nothing and can be captured in a graph.
+ * Returns RIO_ERR_ARG for a NULL ctx / ops / d_rec_off / d_result, n > 0 with a NULL array or a NULL
+ * d_records with records_cap > 0, RIO_ERR_UNSUPPORTED for n >= 2^31 - 1, before any device call. */
+#define RIO_WALENC_RESULT_WORDS 8u
+#define RIO_WALENC_R_N_RECORDS 0u    /* n */
+#define RIO_WALENC_R_BYTES 1u        /* d_rec_off[n]: the record arena's length */
+#define RIO_WALENC_R_N_UPSERTS 2u
+#define RIO_WALENC_R_N_DELETES 3u
+#define RIO_WALENC_R_MAX_KEY_LEN 4u  /* the longest key: what rio_sst_flush_plan takes as max_key_len */
+#define RIO_WALENC_R_FIRST_BAD 5u    /* first refused OP; ~0 = none */
+#define RIO_WALENC_R_BAD_CLASS 6u    /* RIO_WAL_BAD_RANGE */
+/* n records of these arenas never need more: 33 = 3 tags + 3 ten-byte varints per record */
+uint64_t rio_wal_ops_encode_bound(uint64_t n, uint64_t key_bytes, uint64_t value_bytes);
+int rio_wal_ops_encode(rio_ctx* ctx, const rio_ops_view* ops, uint8_t* d_records, uint64_t records_cap,
+                       uint64_t* d_rec_off, uint64_t* d_result, void* stream);
+
 /* ---- bloom filters of tables, and point lookups of a loaded table (rio_bloom.hip) --------------
  * Replaces the writer's filter build (sstables/sstable_writer.go:78-83 NewOptimal, :114-118 one Add per
  * WriteNext, :150-154 WriteFile) and the reader's point lookups (sstable_reader.go:49-65 Contains: filter
@@ -814,6 +853,9 @@ int rio_writer_new(const char* path, uint32_t compression, rio_writer** out);
 /* record == NULL writes a nil record; returns the record's offset in *offset */
 int rio_writer_write(rio_writer* w, const uint8_t* record, uint64_t len, uint64_t* offset);
 uint64_t rio_writer_size(rio_writer* w);
+/* appends len bytes of already-framed records (rio_device_encode's image without its file header, or a
+ * part of it cut at record boundaries) as they are; rio_writer_size grows by len */
+int rio_writer_append_framed(rio_writer* w, const uint8_t* bytes, uint64_t len);
 int rio_writer_close(rio_writer* w);
 /* In-memory encoder used by the generators: appends one record to buf (capacity cap), returns
  * bytes written or 0 if it does not fit. record == NULL => nil record. */
