@@ -204,6 +204,11 @@ struct rio_ctx {
         }
     } fl;
 
+    // rio_mem_index_build (rio_db_host.cpp): the plan's order and keep flags, the compaction's temp and its count
+    struct MemIndex {
+        rio::DevBuf src, keep, cub, n_sel;
+    } mem;
+
     // rio_wal_ops_plan (rio_tables.cpp): the last plan's segments + record bases, the per-record scratch
     // (WalParams, one allocation), scan temp; P holds the scratch pointers for the gather
     struct WalOps {
@@ -247,12 +252,26 @@ struct rio_ctx {
     }
 };
 
+// a stack of loaded tables (rio_super.cpp); rio_db_host.cpp's reader reads its tables
+struct rio_sst_stack {
+    int device = 0;
+    hipStream_t stream = nullptr;  // the creating context's, for calls with a NULL stream
+    uint32_t T = 0;
+    uint64_t max_batch = 0;
+    rio::DevBuf tables, tmp, cub;       // views | prefix pointers | filters | stored-checksum pointers; scan input; scan temp
+    rio::StackParams P{};               // the four table pointers and T
+};
+
 namespace rio {
 
 // the stream of an entry point's `void* stream` argument: the caller's, or the context's own for null
 inline hipStream_t stream_of(const rio_ctx* ctx, void* stream) {
     return stream ? static_cast<hipStream_t>(stream) : ctx->stream;
 }
+
+// rio_tables.cpp: rio_sst_flush_plan after its argument checks; with_crc = false leaves the checksum stage out
+int flush_plan(rio_ctx* ctx, const rio_ops_view* ops, uint32_t mode, uint32_t max_key_len, uint64_t* d_src, uint8_t* d_keep,
+               uint64_t* d_result, void* stream, bool with_crc);
 
 // rio_ctx.cpp
 int ctx_frame_params(rio_ctx* ctx, const uint8_t* d_file, uint64_t len, FrameParams& P, FileArenas& A,

@@ -335,6 +335,43 @@ struct KeysParams {
     uint64_t* key_off;                  // [n_out + 1]
 };
 
+// rio_memidx.hip: a memstore's index (rio_mem_index_build) and the lookup over up to two of them (rio_mem_lookup)
+struct MemBuildParams {
+    rio_ops_view ops;
+    const uint64_t* src;                // [n] the flush plan's order
+    const uint8_t* keep;                // [n] its keep flags
+    uint64_t* order;                    // [n] src compacted by keep
+    uint64_t* pfx;                      // [n] key prefixes of order's ops
+    uint64_t* n_sel;                    // [1] the compaction's count (scratch; the result block's word is read)
+    uint64_t* result;                   // [RIO_MERGE_RESULT_WORDS] the plan's, on the device
+};
+struct MemLookupParams {
+    rio_mem_index i0, i1;               // by value: store 0 and, when n_idx = 2, the newer store 1
+    uint32_t n_idx;
+    const uint8_t* keys;
+    const uint64_t* key_off;            // [n + 1]
+    uint64_t n;
+    uint64_t key_bytes;
+    uint64_t* src;                      // [n] store << RIO_MERGE_ENTRY_BITS | op, or ~0
+};
+// rio_db.hip: the combined read (rio_db_value_plan / rio_db_value_copy)
+struct DbParams {
+    rio_mem_index i0, i1;
+    uint32_t n_idx;
+    const rio_sst_view* views;          // [T] the stack's tables; T = 0: a reader without a stack
+    const uint64_t* const* stored;      // [T]
+    uint32_t T;
+    uint32_t check_crc;
+    const uint64_t* tab_src;            // [n] or null
+    const uint64_t* mem_src;            // [n]
+    uint64_t n;
+    uint8_t* status;                    // [n] RIO_GET_*
+    uint64_t* tmp;                      // [n + 1] scan input (reader scratch)
+    uint64_t* val_off;                  // [n + 1]
+    uint8_t* values;
+    uint64_t values_cap;
+};
+
 // protobuf varint length, and proto.Marshal's size of an IndexEntry {key = 1, valueOffset = 2, checksum = 3}:
 // proto3 omits an empty key and zero scalars (sstables/proto/sstable.proto:5-9)
 #ifdef __HIPCC__

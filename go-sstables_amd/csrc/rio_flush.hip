@@ -38,6 +38,7 @@
 #include "rio_device.h"
 #include "rio_dev_util.h"
 #include "rio_launch.h"
+#include "rio_ops_keys.h"
 
 namespace rio {
 
@@ -48,22 +49,6 @@ constexpr uint64_t kFlushGridCap = 2048;
 
 typedef uint64_t __attribute__((aligned(1))) u64u;
 
-// key of op i: offset and length clamped to the arena and to max_len; false when the clamp changed them
-__device__ __forceinline__ bool key_range(const rio_ops_view& o, uint64_t max_len, uint64_t i, uint64_t& off,
-                                          uint64_t& len) {
-    const uint64_t a = o.key_off[i], b = o.key_off[i + 1];
-    off = umin(a, o.key_bytes);
-    const uint64_t e = umin(umax(b, off), o.key_bytes);
-    len = umin(e - off, max_len);
-    return off == a && e == b && len == e - off;
-}
-// value of op i: [b, e) clamped to the value arena
-__device__ __forceinline__ bool value_range(const rio_ops_view& o, uint64_t i, uint64_t& b, uint64_t& e) {
-    const uint64_t o0 = o.val_off[i], o1 = o.val_off[i + 1];
-    b = umin(o0, o.value_bytes);
-    e = umin(umax(o1, b), o.value_bytes);
-    return b == o0 && e == o1;
-}
 // key of a checked op: the offset clamped again, the length k_flush_check left (at most max_key_len and
 // inside the arena from that offset on)
 __device__ __forceinline__ const uint8_t* key_of(const FlushParams& P, uint64_t op, uint64_t& len) {
@@ -220,8 +205,9 @@ size_t flush_cub_bytes(uint64_t n, uint32_t max_key_len) {
 }
 
 // ev (timing on): kFlushMaxStages + 1 events; ev[k] .. ev[k + 1] bracket stage k (check, the length pass,
-// the chunk passes R-1 .. 0, keep, crc); *n_stages = stages recorded
-hipError_t launch_flush_plan(const FlushParams& P, hipStream_t s, hipEvent_t* ev, uint32_t* n_stages) {
+// the chunk passes R-1 .. 0, keep, crc); *n_stages = stages recorded. with_crc = false leaves the crc stage out
+// (rio_mem_index_build: nothing reads the values' checksums)
+hipError_t launch_flush_plan(const FlushParams& P, hipStream_t s, hipEvent_t* ev, uint32_t* n_stages, bool with_crc) {
     uint32_t k = 0;
     auto stamp = [&]() {
         if (ev) hipEventRecord(ev[k], s);
@@ -256,8 +242,10 @@ hipError_t launch_flush_plan(const FlushParams& P, hipStream_t s, hipEvent_t* ev
     }
     hipLaunchKernelGGL(k_flush_keep, g, b, 0, s, P, (const uint32_t*)P.perm[cur]);
     stamp();
-    hipLaunchKernelGGL(k_flush_crc, g, b, 0, s, P);
-    stamp();
+    if (with_crc) {
+        hipLaunchKernelGGL(k_flush_crc, g, b, 0, s, P);
+        stamp();
+    }
     *n_stages = k - 1;
     return hipGetLastError();
 }

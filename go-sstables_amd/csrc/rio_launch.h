@@ -71,7 +71,16 @@ hipError_t launch_stack_bounds(const StackParams& P, hipStream_t s);
 hipError_t launch_keys_gather(const KeysParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
 // rio_flush.hip
 size_t flush_cub_bytes(uint64_t n, uint32_t max_key_len);
-hipError_t launch_flush_plan(const FlushParams& P, hipStream_t s, hipEvent_t* ev, uint32_t* n_stages);
+hipError_t launch_flush_plan(const FlushParams& P, hipStream_t s, hipEvent_t* ev, uint32_t* n_stages,
+                             bool with_crc = true);
+// rio_memidx.hip
+size_t mem_index_cub_bytes(uint64_t n);
+hipError_t launch_mem_index(const MemBuildParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
+hipError_t launch_mem_lookup(const MemLookupParams& P, hipStream_t s);
+// rio_db.hip
+size_t db_cub_bytes(uint64_t n);
+hipError_t launch_db_value_plan(const DbParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
+hipError_t launch_db_value_copy(const DbParams& P, hipStream_t s);
 // rio_walops.hip
 size_t wal_cub_bytes(uint64_t n);
 hipError_t launch_wal_plan(const WalParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);

@@ -1,7 +1,7 @@
 // rio_sst_keys.h — keys and values of a loaded table on the device (rio_sst_view): the clamped accessors, the
 // 8-byte big-endian key prefix, bytes.Compare and the prefix-probed binary search, and a key's FNV-1 hash with
 // the filter test on it. Shared by the merge plan (rio_compact.hip), the point lookup (rio_bloom.hip) and the
-// stack of tables (rio_stack.hip). Internal to librio.
+// stack of tables (rio_stack.hip); the stack's status rules also by the combined read (rio_db.hip). Internal to librio.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -88,6 +88,32 @@ __device__ __forceinline__ bool entry_of(const rio_sst_view* views, uint32_t T, 
         return false;
     }
     return true;
+}
+
+// status byte (RIO_GET_*) and value length of a lookup's source word over a stack's tables: what Get returns for
+// the entry (sstable_reader.go:67-114). stored = the tables' stored-checksum pointers; check_crc is
+// EnableHashCheckOnReads. k_stack_value_len's rules (rio_stack.hip), which k_db_value_len (rio_db.hip) starts from
+__device__ __forceinline__ void table_status(const rio_sst_view* views, const uint64_t* const* stored_of, uint32_t T,
+                                             uint32_t check_crc, uint64_t word, uint32_t& status, uint64_t& len) {
+    status = RIO_GET_NOT_FOUND;
+    const rio_sst_view* v;
+    uint64_t e;
+    if (entry_of(views, T, word, v, e)) {
+        const uint8_t fl = v->flags[e];
+        const uint64_t* stored = stored_of[word >> RIO_MERGE_ENTRY_BITS];  // entry_of: the table exists
+        if (fl & (RIO_FLAG_CORRUPT | RIO_FLAG_EOF)) {
+            status = RIO_GET_HOST;
+        } else if (check_crc && stored && stored[e] != 0 && stored[e] != v->crc[e]) {
+            status = RIO_GET_HOST;
+        } else if (fl & RIO_FLAG_NIL) {
+            status = RIO_GET_NIL;
+        } else {
+            uint64_t vb, ve;
+            value_at(*v, e, vb, ve);
+            len = ve - vb;
+            status = RIO_GET_VALUE;
+        }
+    }
 }
 
 constexpr uint64_t kFnvBasis = 0xcbf29ce484222325ull, kFnvPrime = 0x100000001b3ull;

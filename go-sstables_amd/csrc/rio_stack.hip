@@ -86,26 +86,8 @@ __global__ void __launch_bounds__(256) k_stack_value_len(StackParams P) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= P.n; i += stride) {
         uint64_t len = 0;
         if (i < P.n) {
-            const uint64_t word = P.src[i];
-            uint32_t status = RIO_GET_NOT_FOUND;
-            const rio_sst_view* v;
-            uint64_t e;
-            if (entry_of(P.views, P.T, word, v, e)) {
-                const uint8_t fl = v->flags[e];
-                const uint64_t* stored = P.stored[word >> RIO_MERGE_ENTRY_BITS];  // entry_of: the table exists
-                if (fl & (RIO_FLAG_CORRUPT | RIO_FLAG_EOF)) {
-                    status = RIO_GET_HOST;
-                } else if (P.flag && stored && stored[e] != 0 && stored[e] != v->crc[e]) {
-                    status = RIO_GET_HOST;
-                } else if (fl & RIO_FLAG_NIL) {
-                    status = RIO_GET_NIL;
-                } else {
-                    uint64_t vb, ve;
-                    value_at(*v, e, vb, ve);
-                    len = ve - vb;
-                    status = RIO_GET_VALUE;
-                }
-            }
+            uint32_t status;
+            table_status(P.views, P.stored, P.T, P.flag, P.src[i], status, len);
             P.status[i] = (uint8_t)status;
         }
         P.tmp[i] = len;

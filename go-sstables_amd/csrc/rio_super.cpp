@@ -11,15 +11,6 @@
 
 using namespace rio;
 
-struct rio_sst_stack {
-    int device = 0;
-    hipStream_t stream = nullptr;  // the creating context's, for calls with a NULL stream
-    uint32_t T = 0;
-    uint64_t max_batch = 0;
-    DevBuf tables, tmp, cub;       // views | prefix pointers | filters | stored-checksum pointers; scan input; scan temp
-    StackParams P{};               // the four table pointers and T
-};
-
 namespace {
 
 hipStream_t stream_of(const rio_sst_stack* st, void* stream) {

@@ -267,6 +267,12 @@ extern "C" int rio_sst_flush_plan(rio_ctx* ctx, const rio_ops_view* ops, uint32_
     if (n && (!ops->keys || !ops->key_off || !ops->values || !ops->val_off || !ops->flags || !d_src || !d_keep))
         return RIO_ERR_ARG;
     if (n >= (1ull << 31) - 1 || max_key_len > RIO_FLUSH_MAX_KEY_LEN) return RIO_ERR_UNSUPPORTED;
+    return flush_plan(ctx, ops, mode, max_key_len, d_src, d_keep, d_result, stream, true);
+}
+
+int rio::flush_plan(rio_ctx* ctx, const rio_ops_view* ops, uint32_t mode, uint32_t max_key_len, uint64_t* d_src,
+                    uint8_t* d_keep, uint64_t* d_result, void* stream, bool with_crc) {
+    const uint64_t n = ops->n;
     // from here on *ctx is read
     HIP_TRY(hipSetDevice(ctx->device));
     rio_ctx::Merge& M = ctx->mrg;
@@ -326,7 +332,7 @@ extern "C" int rio_sst_flush_plan(rio_ctx* ctx, const rio_ops_view* ops, uint32_
     P.result = d_result;
     F.stages = 0;
     uint32_t stages = 0;
-    HIP_TRY(launch_flush_plan(P, s, ev, &stages));
+    HIP_TRY(launch_flush_plan(P, s, ev, &stages, with_crc));
     F.stages = ev ? stages : 0;
     M.T = 1;
     M.N = n;

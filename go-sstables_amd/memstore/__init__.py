@@ -8,6 +8,12 @@ ones under Flush), then the back end merge-compaction uses (sstables.merger.enco
 encode, index entries, index encode). The three files are byte-identical to what the reference's
 SSTableStreamWriter writes for the same sorted pairs. None is Go's nil; b"" is an empty non-nil key or
 value. Functions return Go-style error values. There is no CPU fallback.
+
+Batched point reads search the log where it lies on the device: DeviceMemIndex makes an uploaded log searchable
+in place (rio_mem_index_build, csrc/rio_memidx.hip: the flush plan's order compacted to the latest op of every
+key, 16 bytes per distinct key, no key or value copied), MemStore.GetBatch / ContainsBatch answer what loops of
+Get / Contains answer through it. The index is rebuilt, from the log's first op, at the first batched read after
+the log has grown.
 """
 from __future__ import annotations
 
@@ -90,6 +96,174 @@ def upload_ops(device: int, keys: bytearray, key_off, values: bytearray, val_off
                      max_key_len)
 
 
+def upload_queries(device: int, keys):
+    """Query keys as the arena every lookup takes: (uint8 arena, int64 offsets[n + 1], arena length) on `device`."""
+    import numpy as np
+    import torch
+
+    arena = b"".join(keys)
+    off = np.zeros(len(keys) + 1, dtype=np.int64)
+    np.cumsum([len(k) for k in keys], out=off[1:])
+    dev = f"cuda:{device}"
+    d_keys = torch.from_numpy(np.frombuffer(arena + b"\0", dtype=np.uint8).copy()).to(dev)
+    return d_keys, torch.from_numpy(off).to(dev), len(arena)
+
+
+def index_array(indexes):
+    """The rio_mem_index array of `indexes` (DeviceMemIndex, oldest first: the write store last)."""
+    return (L.MemIndex * len(indexes))(*[i.view for i in indexes])
+
+
+def read_piece(ctx, device: int, st, reader, stack, idx, p_keys, p_off, n: int, nbytes: int):
+    """One batch of DB.GetBytes on stream `st`: rio_sst_stack_lookup (stack: the handle or None), rio_mem_lookup,
+    rio_db_value_plan, the 8-byte read that sizes the values, rio_db_value_copy. idx: index_array(...); reader: a
+    rio_db_reader over `stack`. Returns (mem_src, tab_src or None, status, val_off, values) as device tensors."""
+    import torch
+
+    from sstables.merger import check_status
+
+    lib, dev, k = L.lib(), f"cuda:{device}", len(idx)
+    p_idx = ctypes.addressof(idx)
+    tab = None
+    if stack is not None:
+        tab = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        check_status(lib.rio_sst_stack_lookup(stack, 0, p_keys, p_off, n, nbytes, tab.data_ptr(), st), "rio_sst_stack_lookup")
+    p_tab = None if tab is None else tab.data_ptr()
+    mem = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    status = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+    val_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    check_status(lib.rio_mem_lookup(ctx, p_idx, k, p_keys, p_off, n, nbytes, mem.data_ptr(), st), "rio_mem_lookup")
+    check_status(lib.rio_db_value_plan(reader, p_idx, k, p_tab, mem.data_ptr(), n, 1, status.data_ptr(),
+                                       val_off.data_ptr(), st), "rio_db_value_plan")
+    total = int(val_off[n].item())  # the one round trip: the value arena's size
+    values = torch.empty(total + L.RIO_DEVICE_PAD, dtype=torch.uint8, device=dev)
+    check_status(lib.rio_db_value_copy(reader, p_idx, k, p_tab, mem.data_ptr(), status.data_ptr(), n, val_off.data_ptr(),
+                                       values.data_ptr(), total, st), "rio_db_value_copy")
+    return mem[:n], None if tab is None else tab[:n], status[:n], val_off, values[:total]
+
+
+class DeviceMemIndex:
+    """A searchable snapshot of an op log in device memory (rio_mem_index_build): `order` (the op of every distinct
+    key's latest op, keys ascending) and `pfx` (those keys' 8-byte prefixes), n_keys in the result block ON THE
+    DEVICE. The log is not copied; the DeviceOps is kept alive here. Get / Contains / GetBatch / ContainsBatch are
+    MemStore's (memstore.go:92-123), answered by rio_mem_lookup: a log that never was on the host can be read."""
+
+    def __init__(self, ops: DeviceOps):
+        self.device = ops.device
+        self.order = self.pfx = self.result = None
+        self._reader, self._reader_cap = None, 0
+        self.rebuild(ops)
+
+    def rebuild(self, ops: DeviceOps):
+        """Index `ops` (the log grown longer, or another log) into the same buffers while it fits them."""
+        import torch
+
+        from sstables import UnsupportedError
+        from sstables.merger import check_status, on_device_stream
+
+        dev, n = f"cuda:{self.device}", int(ops.n)
+        with torch.cuda.device(self.device):
+            if self.result is None:
+                self.result = torch.zeros(L.RIO_MERGE_RESULT_WORDS, dtype=torch.int64, device=dev)
+            if self.order is None or n > self.order.numel():
+                self.order = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+                self.pfx = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+            self.ops, self._rejected = ops, None
+            self.err = None
+            if ops.max_key_len > L.RIO_FLUSH_MAX_KEY_LEN:  # the device rejects the log too: n_keys = 0
+                self.err = UnsupportedError(f"a key of {ops.max_key_len} bytes: the device orders keys of up to "
+                                            f"{L.RIO_FLUSH_MAX_KEY_LEN}")
+            bound = min(int(ops.max_key_len), L.RIO_FLUSH_MAX_KEY_LEN)
+            on_device_stream(self.device, lambda st: check_status(
+                L.lib().rio_mem_index_build(L.default_ctx(self.device), ctypes.addressof(ops.view), bound,
+                                            self.order.data_ptr(), self.pfx.data_ptr(), self.result.data_ptr(), st),
+                "rio_mem_index_build"))
+        return self
+
+    @property
+    def view(self):
+        return L.MemIndex(ops=self.ops.view, order=self.order.data_ptr(), pfx=self.pfx.data_ptr(),
+                          result=self.result.data_ptr())
+
+    def result_words(self):
+        """The build's result block, read from the device."""
+        return [x & _NONE for x in self.result.cpu().tolist()]
+
+    def n_keys(self) -> int:
+        return self.result_words()[L.RIO_MERGE_R_N_OUT]
+
+    def rejected(self):
+        """None, or the error of a log the build refused (read from the device once per build)."""
+        if self._rejected is None:
+            bad = self.result_words()[L.RIO_MERGE_R_UNSORTED]
+            self._rejected = False if bad == _NONE else GoError(f"memstore index: op {bad} of the log was rejected")
+        return self.err or self._rejected or None
+
+    def _free_reader(self):
+        if self._reader is not None:
+            h, self._reader = self._reader, None
+            L.lib().rio_db_reader_free(h)
+
+    def __del__(self):
+        try:
+            self._free_reader()
+        except Exception:  # interpreter shutdown: the library may be gone
+            pass
+
+    def _get(self, keys):
+        """(mem_src, status, val_off, values) on the host for keys (bytes), through a reader without tables."""
+        import torch
+
+        from sstables.merger import check_status, on_device_stream
+
+        n = len(keys)
+        with torch.cuda.device(self.device):
+            ctx = L.default_ctx(self.device)
+            if n > self._reader_cap:
+                self._free_reader()
+                h, cap = ctypes.c_void_p(), max(n, 1024)
+                check_status(L.lib().rio_db_reader_create(ctx, None, cap, ctypes.byref(h)), "rio_db_reader_create")
+                self._reader, self._reader_cap = h, cap
+
+            def run(st):
+                d_keys, d_off, nbytes = upload_queries(self.device, keys)
+                return read_piece(ctx, self.device, st, self._reader, None, index_array([self]), d_keys.data_ptr(),
+                                  d_off.data_ptr(), n, nbytes)
+
+            mem, _, status, val_off, values = on_device_stream(self.device, run)
+            return ([x & _NONE for x in mem.cpu().tolist()], status.cpu().tolist(), val_off.cpu().tolist(),
+                    bytes(values.cpu().numpy()))
+
+    def GetBatch(self, keys):  # noqa: N802
+        """[(value, err)] per key: what a loop of MemStore.Get returns (KeyNotFound / KeyTombstoned themselves)."""
+        keys = [_key(k) for k in keys]
+        err = self.rejected()
+        if err is not None:
+            return [(None, err) for _ in keys]
+        if not keys:
+            return []
+        mem, status, off, val = self._get(keys)
+        return [(val[off[i]:off[i + 1]], None) if s == L.RIO_GET_MEM_VALUE
+                else (None, KeyNotFound if mem[i] == _NONE else KeyTombstoned) for i, s in enumerate(status)]
+
+    def ContainsBatch(self, keys):  # noqa: N802
+        """[found] per key: what a loop of MemStore.Contains returns. A log the device refuses raises its error
+        (a bool cannot carry it)."""
+        keys = [_key(k) for k in keys]
+        err = self.rejected()
+        if err is not None:
+            raise err
+        if not keys:
+            return []
+        return [s == L.RIO_GET_MEM_VALUE for s in self._get(keys)[1]]
+
+    def Get(self, key):  # noqa: N802
+        return self.GetBatch([key])[0]
+
+    def Contains(self, key) -> bool:  # noqa: N802
+        return self.ContainsBatch([key])[0]
+
+
 class _Iterator:
     """SkipListSStableIterator (memstore/sstable_iterator.go): keys ascending, nil for a tombstoned key."""
 
@@ -116,6 +290,29 @@ class MemStore:
         self._key_off, self._val_off = [0], [0]
         self._flags = bytearray()
         self._max_key_len = 0
+        self._idx, self._idx_n = None, -1  # DeviceMemIndex over the uploaded log, and the log length it covers
+
+    def _index(self) -> "DeviceMemIndex":
+        """The device index of the log as it stands: uploaded and rebuilt when the log has grown since."""
+        import torch
+
+        n = len(self._flags)
+        if self._idx is None or self._idx_n != n:
+            with torch.cuda.device(self.device):
+                ops = upload_ops(self.device, self._keys, self._key_off, self._values, self._val_off, self._flags,
+                                 self._max_key_len)
+                self._idx = DeviceMemIndex(ops) if self._idx is None else self._idx.rebuild(ops)
+            self._idx_n = n
+        return self._idx
+
+    def GetBatch(self, keys):  # noqa: N802
+        """[(value, err)] per key, equal to a loop of Get; the search runs on the device. A memstore with a key
+        longer than RIO_FLUSH_MAX_KEY_LEN returns UnsupportedError per key, as its flush does."""
+        return self._index().GetBatch(keys)
+
+    def ContainsBatch(self, keys):  # noqa: N802
+        """[found] per key, equal to a loop of Contains; raises UnsupportedError for such a memstore."""
+        return self._index().ContainsBatch(keys)
 
     def _log(self, key: bytes, value):
         self._keys += key

@@ -148,6 +148,21 @@ class OpsView(ctypes.Structure):
     ]
 
 
+RIO_DB_MAX_MEMSTORES = 2
+RIO_GET_MEM_VALUE = 4  # rio_db_value_plan: a memstore's value answers
+
+
+class MemIndex(ctypes.Structure):
+    """rio_mem_index (include/rio.h): an op log with its searchable order, by value."""
+
+    _fields_ = [
+        ("ops", OpsView),
+        ("order", c_void_p),
+        ("pfx", c_void_p),
+        ("result", c_void_p),
+    ]
+
+
 RIO_WAL_MAX_SEGMENTS = 4096
 RIO_WAL_RESULT_WORDS = 8
 (RIO_WAL_R_N_RECORDS, RIO_WAL_R_N_OPS, RIO_WAL_R_KEY_BYTES, RIO_WAL_R_VALUE_BYTES, RIO_WAL_R_MAX_KEY_LEN,
@@ -314,6 +329,15 @@ _SIGS = {
     "rio_sst_keys_gather": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p]),
     "rio_sst_flush_plan": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rio_sst_flush_stage_ms": (c_int, [c_void_p, POINTER(c_float), c_int]),
+    "rio_mem_index_build": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rio_mem_lookup": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p]),
+    "rio_db_reader_create": (c_int, [c_void_p, c_void_p, c_uint64, POINTER(c_void_p)]),
+    "rio_db_reader_free": (None, [c_void_p]),
+    "rio_db_value_plan": (
+        c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p]),
+    "rio_db_value_copy": (
+        c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64,
+                c_void_p]),
     "rio_wal_ops_plan": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),
     "rio_wal_ops_gather": (
         c_int, [c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p,

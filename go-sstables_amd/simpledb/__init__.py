@@ -11,6 +11,12 @@ The write side is batched the same way: a WriteBatch holds db.PutBytes / db.Dele
 the memstore's op log, append_batch marshals every op into its WalMutation record on the device
 (rio_wal_ops_encode, csrc/rio_walenc.hip), frames the records into WAL file images (rio_device_encode) and
 writes them through wal.Appender.AppendFramed; the same device arrays then go to memstore.flush_ops_on_device.
+
+The read side is DBReadView: db.GetBytes (db.go:197-242) over a table stack and the memstore pair (RWMemstore,
+rw_memstore.go), one key at a time on the host as the reference runs it, and a batch of keys on the device
+(rio_sst_stack_lookup, rio_mem_lookup, rio_db_value_plan / _copy; csrc/rio_memidx.hip, csrc/rio_db.hip). A store
+may be a memstore.DeviceMemIndex: a log that append_batch returned or wal_ops_on_device recovered is read without
+ever having been on the host. There is no DB object (Open / Close, rotation, background flush and compaction).
 Functions return Go-style error values. There is no CPU fallback.
 """
 from __future__ import annotations
@@ -358,3 +364,249 @@ def _reset_dir(base_path: str):
     except OSError as e:
         return GoError(str(e))
     return None
+
+
+ErrNotFound = GoError("ErrNotFound")  # db.go:35
+
+
+class RWMemstore:
+    """simpledb/rw_memstore.go: two memstores, one for reading (the one being flushed), one for writing; the one
+    that writes takes precedence for the same key. The stores are memstore.MemStores, or anything with their
+    calls (a memstore.DeviceMemIndex for the read paths)."""
+
+    def __init__(self, readStore, writeStore):  # noqa: N803
+        self.readStore, self.writeStore = readStore, writeStore
+
+    def Contains(self, key) -> bool:  # noqa: N802
+        return self.writeStore.Contains(key) or self.readStore.Contains(key)
+
+    def Get(self, key):  # noqa: N802
+        """rw_memstore.go:22-36: only the write store's KeyNotFound asks the read store; its tombstone answers."""
+        from memstore import KeyNotFound
+
+        v, err = self.writeStore.Get(key)
+        if err is not None:
+            if err is KeyNotFound:
+                return self.readStore.Get(key)
+            return None, err
+        return v, None
+
+    def Add(self, key, value):  # noqa: N802
+        return self.writeStore.Add(key, value)
+
+    def Upsert(self, key, value):  # noqa: N802
+        return self.writeStore.Upsert(key, value)
+
+    def Delete(self, key):  # noqa: N802
+        from memstore import KeyNotFound
+
+        err = self.writeStore.Delete(key)
+        if err is KeyNotFound:
+            return self.Tombstone(key)
+        return err
+
+    def DeleteIfExists(self, key):  # noqa: N802
+        return self.Delete(key)
+
+    def Tombstone(self, key):  # noqa: N802
+        return self.writeStore.Tombstone(key)
+
+    def EstimatedSizeInBytes(self) -> int:  # noqa: N802
+        return self.writeStore.EstimatedSizeInBytes()
+
+    def SStableIterator(self):  # noqa: N802
+        return self.writeStore.SStableIterator()
+
+    def Flush(self, *opts):  # noqa: N802
+        return self.writeStore.Flush(*opts)
+
+    def Size(self) -> int:  # noqa: N802
+        return self.writeStore.Size()
+
+
+class _NoReadStore:
+    """The read store of a view that has none: holds no key."""
+
+    def Get(self, key):  # noqa: N802
+        from memstore import KeyNotFound
+
+        return None, KeyNotFound
+
+    def Contains(self, key) -> bool:  # noqa: N802
+        return False
+
+
+class DBReadView:
+    """DB.GetBytes / Get (db.go:184-242) over `tables` (a sstables.SuperSSTableReader, or None for a database
+    without tables yet), the write memstore and the read memstore (the one being flushed, or None). A store is a
+    memstore.MemStore or a memstore.DeviceMemIndex. GetBytes / Get run the reference's host sequence; GetBatch /
+    GetBatchOnDevice answer a batch on the device. The open / closed checks of db.go:201-207 belong to the DB
+    object, which this is not; bytes comparator only."""
+
+    def __init__(self, tables, write_store, read_store=None, max_batch: int = 1 << 20):
+        self.tables, self.write_store, self.read_store = tables, write_store, read_store
+        self.max_batch = int(max_batch) if tables is None else min(int(max_batch), tables.max_batch)
+        self.memstore = RWMemstore(_NoReadStore() if read_store is None else read_store, write_store)
+        self._reader, self._reader_stack = None, None
+
+    # ---- the reference's host sequence --------------------------------------------------------------------------
+
+    def GetBytes(self, key):  # noqa: N802
+        """db.go:197-242: the tables first (their error is returned before the memstore is asked), then the
+        memstore, which wins with a value and hides the key with a tombstone."""
+        from memstore import KeyNotFound, KeyTombstoned
+        from sstables import NotFound
+
+        key = bytes(key or b"")
+        tab_val, tab_missing = None, True
+        if self.tables is not None:
+            tab_val, err = self.tables.Get(key)
+            if err is not None:
+                if err is not NotFound:
+                    return None, err
+            elif tab_val is not None and len(tab_val) != 0:
+                tab_missing = False
+        mem_val, err = self.memstore.Get(key)
+        if err is not None:
+            if err is KeyNotFound:
+                return (None, ErrNotFound) if tab_missing else (tab_val, None)
+            if err is KeyTombstoned:
+                return None, ErrNotFound
+            return None, err
+        return mem_val, None
+
+    def Get(self, key: str):  # noqa: N802
+        """db.Get (db.go:184-195)."""
+        v, err = self.GetBytes(key.encode())
+        if err is not None:
+            return "", err
+        return v.decode(errors="surrogateescape"), None
+
+    # ---- the batch on the device --------------------------------------------------------------------------------
+
+    @property
+    def _device(self) -> int:
+        return self.tables._device if self.tables is not None and self.tables.readers else self.write_store.device
+
+    def _indexes(self):
+        """The stores' device indexes, oldest first (the write store last)."""
+        from memstore import MemStore
+
+        stores = [s for s in (self.read_store, self.write_store) if s is not None]
+        return [s._index() if isinstance(s, MemStore) else s for s in stores]
+
+    def _host_only(self):
+        """The stack's own rule: None, or why its batches are answered on the host."""
+        from sstables import UnsupportedError
+
+        if self.tables is None:
+            return None
+        err = self.tables._unsupported()
+        if err is None and any(r.t.v0 for r in self.tables.readers):
+            err = UnsupportedError("a stack with a v0 table answers GetBatch on the host: no device values")
+        return err
+
+    def _free_reader(self):
+        if self._reader is not None:
+            h, self._reader = self._reader, None
+            L.lib().rio_db_reader_free(h)
+
+    def Close(self):  # noqa: N802
+        """Frees the reader handle; the tables and the stores are the caller's."""
+        self._free_reader()
+        return None
+
+    def __del__(self):
+        try:
+            self._free_reader()
+        except Exception:  # interpreter shutdown: the library may be gone
+            pass
+
+    def _ensure_reader(self, st):
+        """The tables' stack, then the reader over it (again when the stack was freed and made anew)."""
+        from sstables.merger import check_status
+
+        stack = None
+        if self.tables is not None:
+            self.tables._ensure_stack(st)
+            stack = self.tables._stack
+        key = None if stack is None else stack.value
+        if self._reader is None or self._reader_stack != key:
+            self._free_reader()
+            h = ctypes.c_void_p()
+            check_status(L.lib().rio_db_reader_create(L.default_ctx(self._device), stack, self.max_batch, ctypes.byref(h)),
+                         "rio_db_reader_create")
+            self._reader, self._reader_stack = h, key
+        return stack
+
+    def GetBatchOnDevice(self, d_keys, d_key_off, n: int):  # noqa: N802
+        """(mem_src, tab_src, status, val_off, values) as device tensors for n <= max_batch query keys already on
+        the device (uint8 arena d_keys, int64 offsets d_key_off[n + 1]); the only host read is the 8 bytes that
+        size `values`. mem_src[i] = store << 40 | op or -1 (store 1 = the write store when there are two),
+        tab_src[i] = table << 40 | entry or -1 (None without tables), status[i] one of RIO_GET_* (RIO_GET_MEM_VALUE:
+        the memstore's value), value i = values[val_off[i]:val_off[i + 1]]."""
+        import torch
+
+        from memstore import index_array, read_piece
+        from sstables.merger import on_device_stream
+
+        err = self._host_only()
+        idx = self._indexes()
+        for i in idx:
+            err = err or i.err
+        if err is not None:
+            raise err
+        device = self._device
+        with torch.cuda.device(device):
+            def run(st):
+                stack = self._ensure_reader(st)
+                return read_piece(L.default_ctx(device), device, st, self._reader, stack, index_array(idx),
+                                  d_keys.data_ptr(), d_key_off.data_ptr(), n, d_keys.numel())
+
+            return on_device_stream(device, run)
+
+    def GetBatch(self, keys):  # noqa: N802
+        """[(value, err)] per key, equal to a loop of GetBytes, in pieces of max_batch. A RIO_GET_HOST entry gets
+        its error from the owning reader, as SuperSSTableReader.GetBatch does."""
+        import torch
+
+        from memstore import index_array, read_piece, upload_queries
+        from sstables.merger import on_device_stream
+
+        keys = [bytes(k or b"") for k in keys]
+        if self._host_only() is not None:
+            return [self.GetBytes(k) for k in keys]
+        idx = self._indexes()
+        for i in idx:
+            err = i.rejected()
+            if err is not None:
+                return [(None, err) for _ in keys]
+        n = len(keys)
+        if n == 0:
+            return []
+        device = self._device
+        with torch.cuda.device(device):
+            def run(st):
+                stack = self._ensure_reader(st)
+                d_keys, d_off, nbytes = upload_queries(device, keys)
+                arr, ctx = index_array(idx), L.default_ctx(device)
+                return [read_piece(ctx, device, st, self._reader, stack, arr, d_keys.data_ptr(), d_off.data_ptr() + 8 * a,
+                                   min(a + self.max_batch, n) - a, nbytes) for a in range(0, n, self.max_batch)]
+
+            out = []
+            for _, tab, status, val_off, values in on_device_stream(device, run):
+                h_status, h_off, h_val = status.cpu().tolist(), val_off.cpu().tolist(), bytes(values.cpu().numpy())
+                h_tab = None
+                for i, s in enumerate(h_status):
+                    if s in (L.RIO_GET_VALUE, L.RIO_GET_MEM_VALUE):
+                        out.append((h_val[h_off[i]:h_off[i + 1]], None))
+                    elif s == L.RIO_GET_HOST:
+                        h_tab = tab.cpu().tolist() if h_tab is None else h_tab
+                        w = h_tab[i] & _NONE
+                        r = self.tables.readers[w >> L.RIO_MERGE_ENTRY_BITS]
+                        _, e = r._value_at(w & ((1 << L.RIO_MERGE_ENTRY_BITS) - 1), r.opts.skipHashCheckOnRead)
+                        # a read the host can make after all: the key's answer by the host sequence
+                        out.append((None, e) if e is not None else self.GetBytes(keys[len(out)]))
+                    else:
+                        out.append((None, ErrNotFound))
+            return out

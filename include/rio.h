@@ -698,6 +698,85 @@ int rio_sst_stack_bounds(rio_sst_stack* stack, const uint8_t* d_keys, const uint
 int rio_sst_keys_gather(rio_ctx* ctx, const uint64_t* d_out_src, uint64_t n_out, uint8_t* d_keys, uint64_t keys_cap,
                         uint64_t* d_key_off, void* stream);
 
+/* ---- batched GetBytes: memstores over the table stack (rio_memidx.hip, rio_db.hip) -------------
+ * Replaces a loop of DB.GetBytes (simpledb/db.go:197-242) over a batch of keys: the table stack's Get
+ * (currentSSTable().Get, :212), then the memstore pair's Get (RWMemstore.Get, simpledb/rw_memstore.go:22-36:
+ * the write store, and only on its KeyNotFound the read store, the one being flushed), combined by the rules
+ * of :213-241. A memstore is the op log of rio_ops_view as it lies in device memory; rio_mem_index_build
+ * makes it searchable in place, without copying a key or a value.
+ *
+ * An index is 16 bytes per distinct key: d_order[j] = the op index of the latest op of the j-th distinct key
+ * in bytes.Compare order (nil ops included: the state FlushWithTombstones would write, memstore.go:189-238),
+ * d_pfx[j] = that key's first 8 bytes as a big-endian word, zero-padded (the probe word of rio_sst_key_prefixes).
+ * Only the first n_keys entries of both are meaningful; n_keys is the RIO_MERGE_R_N_OUT word of d_result, the
+ * block of rio_sst_flush_plan, which stays in DEVICE memory: the lookups read n_keys there and clamp it to
+ * ops.n, so no host read stands between a build and a lookup, and a lookup captured into a hipGraph sees the
+ * index of a later build into the same buffers. RIO_MERGE_R_UNSORTED holds the first rejected op as for the
+ * flush plan (a range that leaves its arena, a key longer than max_key_len); such a log leaves n_keys = 0.
+ * The build runs the flush plan's sort and keep stages under RIO_FLUSH_WITH_TOMBSTONES (not its checksums), one
+ * stream compaction of the kept positions and one kernel for the prefixes. It is a plan call: it REPLACES the
+ * context's last plan and leaves none (rio_sst_merge_gather / rio_sst_keys_gather / rio_sst_index_encode return
+ * RIO_ERR_STATE until the next rio_sst_merge_plan / rio_sst_flush_plan); rio_sst_flush_stage_ms reports its
+ * stages. Scratch (the plan's, 9 bytes per op and the compaction's temp) is sized in the call, nothing is
+ * allocated afterwards. Stream-ordered (NULL = the ctx stream), never waits for the stream. The index costs one
+ * sort of the whole log: a log that has grown is indexed again from its first op.
+ * Returns RIO_ERR_ARG for a NULL ctx / ops / d_result or n > 0 with a NULL array, RIO_ERR_UNSUPPORTED for
+ * n >= 2^31 - 1 or max_key_len > RIO_FLUSH_MAX_KEY_LEN, before any device call. */
+#define RIO_DB_MAX_MEMSTORES 2u
+typedef struct rio_mem_index {
+    rio_ops_view ops;        /* the log the index points into; ops.n bounds every op index read back */
+    const uint64_t* order;   /* [ops.n] rio_mem_index_build's d_order */
+    const uint64_t* pfx;     /* [ops.n] its d_pfx */
+    const uint64_t* result;  /* its d_result (device memory) */
+} rio_mem_index;
+int rio_mem_index_build(rio_ctx* ctx, const rio_ops_view* ops, uint32_t max_key_len, uint64_t* d_order, uint64_t* d_pfx,
+                        uint64_t* d_result, void* stream);
+/* d_mem_src[i] = store << RIO_MERGE_ENTRY_BITS | op of the newest store of idx[0 .. n_idx) that holds query i =
+ * d_keys[d_key_off[i] .. d_key_off[i + 1]), or ~0. Position is age, the highest is the newest (the write store
+ * after the read store), as for tables. The first store that holds the key answers, also when its op is nil:
+ * a tombstone in the write store ends the search (rw_memstore.go:25-33 returns KeyTombstoned without asking the
+ * read store). The indexes travel by value in the kernel's arguments: nothing is copied to the device, the call
+ * can be captured into a hipGraph. key_bytes is the query arena's length; nothing past it is read. Every index
+ * read back from a buffer is clamped (n_keys to ops.n, an op to [0, ops.n), ranges to their arenas): a wrong
+ * input gives ~0 or a wrong op, never an out-of-range access.
+ * RIO_ERR_ARG before any device call: a NULL ctx / idx, n_idx = 0 or above RIO_DB_MAX_MEMSTORES, an index with
+ * a NULL result block or with ops.n > 0 and a NULL array, n > 0 with a NULL array; RIO_ERR_UNSUPPORTED for
+ * n >= 2^31 - 1 or an index of 2^40 ops and more. n = 0 is a no-op. */
+int rio_mem_lookup(rio_ctx* ctx, const rio_mem_index* idx, uint32_t n_idx, const uint8_t* d_keys,
+                   const uint64_t* d_key_off, uint64_t n, uint64_t key_bytes, uint64_t* d_mem_src, void* stream);
+/* The combined read. A reader owns the scan's scratch for batches of up to max_batch queries (8 bytes per query
+ * and the scan's temp); stack = NULL is a database without tables yet. The stack must outlive the reader. After
+ * create no reader call allocates, waits for the device or reads a host array.
+ * RIO_ERR_ARG for a NULL ctx / out or max_batch = 0, RIO_ERR_UNSUPPORTED for max_batch >= 2^31 - 1, before any
+ * device call. */
+typedef struct rio_db_reader rio_db_reader;
+#define RIO_GET_MEM_VALUE 4u /* rio_db_value_plan: a memstore's value answers (an empty one too: length 0) */
+int rio_db_reader_create(rio_ctx* ctx, rio_sst_stack* stack, uint64_t max_batch, rio_db_reader** out);
+void rio_db_reader_free(rio_db_reader* reader); /* NULL is accepted */
+/* Per query a status byte and d_val_off[n + 1], the exclusive scan of the value lengths, from d_tab_src =
+ * rio_sst_stack_lookup(gated = 0)'s words (NULL without a stack: no table holds any key) and d_mem_src =
+ * rio_mem_lookup's over the same idx. The table's own status is rio_sst_stack_value_plan's (check_crc as there).
+ * db.go:197-242, the first rule that matches:
+ *   1. the table status is RIO_GET_HOST: RIO_GET_HOST. The reference returns the table's error before it asks
+ *      the memstore (:212-218), so also when a memstore holds the key
+ *   2. a memstore holds the key with a non-nil op: RIO_GET_MEM_VALUE with the op's value length, 0 included
+ *      (:240-241 returns the memstore's empty value without an error)
+ *   3. a memstore holds the key with a nil op: RIO_GET_NOT_FOUND whatever the tables hold (:231-234)
+ *   4. the table status is RIO_GET_VALUE with length > 0: RIO_GET_VALUE (:228-229)
+ *   5. RIO_GET_NOT_FOUND: the table statuses NOT_FOUND and NIL, and VALUE of length 0 (:214-221, :226-227)
+ * RIO_ERR_ARG: a NULL reader / idx / d_val_off, n_idx = 0 or above RIO_DB_MAX_MEMSTORES, an index refused as by
+ * rio_mem_lookup, n > 0 with a NULL d_mem_src / d_status, d_tab_src given to a reader without a stack,
+ * n > max_batch. */
+int rio_db_value_plan(rio_db_reader* reader, const rio_mem_index* idx, uint32_t n_idx, const uint64_t* d_tab_src,
+                      const uint64_t* d_mem_src, uint64_t n, uint32_t check_crc, uint8_t* d_status, uint64_t* d_val_off,
+                      void* stream);
+/* The values back to back in query order: value i to d_values[d_val_off[i] .. d_val_off[i + 1]), from the op
+ * log's value arena (RIO_GET_MEM_VALUE) or the table's data arena (RIO_GET_VALUE). A value that would pass
+ * values_cap is not copied. Arguments as for rio_db_value_plan, with its d_status and d_val_off. */
+int rio_db_value_copy(rio_db_reader* reader, const rio_mem_index* idx, uint32_t n_idx, const uint64_t* d_tab_src,
+                      const uint64_t* d_mem_src, const uint8_t* d_status, uint64_t n, const uint64_t* d_val_off,
+                      uint8_t* d_values, uint64_t values_cap, void* stream);
+
 /* ---- DiskKeyIndex lookups (sstables/disk_key_index.go:87-140) --------------------------------
  * Batched DiskKeyIndex.Get / Contains / IteratorStartingAt: one result per query key, each the
  * reference's binarySearch over the byte offsets of an uncompressed index.rio with every probe
