@@ -57,14 +57,16 @@ extern "C" uint64_t rio_max_records(uint64_t len) {
 // context
 // ------------------------------------------------------------------------------------------
 // mean bytes per record for which the auto walk takes k_walk_lane (round 5 A/B on MI355X, 16 KiB lane chunks:
-// 1 KiB incompressible records walk 0.269 -> 0.142 ms; 560-byte records even; 48-byte and 36 KiB records
-// slower, so those keep k_walk)
+// 1 KiB incompressible records walk 0.269 -> 0.142 ms; 48-byte and 36 KiB records slower, so those keep k_walk)
 constexpr uint64_t kLaneWalkMin = 768, kLaneWalkMax = 8192, kLaneWalkChunks = 32768;
-// 512..767-byte records take the lane walk only on files of kLaneWalkSmallChunks lane chunks and more (~30 hops per
-// lane want a wave per SIMD of lanes): C2's 561-byte records in 535 MiB measured even (walk 0.143 -> 0.155 ms, decode
-// 0.999 -> 0.988), the same records in a 5 GB file walk 1.10 -> 0.67 ms (profiles/r5/r5be_lane_walk_min_ab.txt).
-// RIO_LANE_WALK_MIN overrides kLaneWalkSmallMin.
-constexpr uint64_t kLaneWalkSmallMin = 512, kLaneWalkSmallChunks = 65536;
+// 512..767-byte records take the lane walk on files of kLaneWalkSmallChunks lane chunks and more. With three 8-byte slot
+// stores per record C2's 561-byte records in 535 MiB measured even against the wave walk, and this was 65536
+// (profiles/r5/r5be_lane_walk_min_ab.txt); with one 16-byte slot store per record the lane walk frames C2 0.025 ms faster
+// (walk + scan + place 0.178 -> 0.153 ms, value 448.9 -> 463.5 GiB/s, medians of five alternated runs, lines "c2 parent" /
+// "c2 new" of profiles/r7/r7b_slots_ab.txt), so the class takes it from the same file size as the larger records.
+// Lane chunk: 16 KiB like theirs; 12 KiB framed another 0.010 ms faster with a value inside the run-to-run spread,
+// 8 KiB and 24 KiB slower (lines "lane8k" / "lane12k" / "lane24k" there). RIO_LANE_WALK_MIN overrides kLaneWalkSmallMin.
+constexpr uint64_t kLaneWalkSmallMin = 512, kLaneWalkSmallChunks = 32768;
 // records of more than kLaneWalkMax bytes on average: wave-walk chunks of at least kBigRecordChunk (a 32 KiB chunk holds
 // at most a few such records and the placement runs a wave per chunk with most lanes idle: C4 place 0.123 -> 0.076 ms,
 // walk 0.61 -> 0.585, +1.2 %, profiles/r5/r5bl_c4_chunk_ab.txt); not when RIO_CHUNK_BYTES sets the size
@@ -84,7 +86,7 @@ static uint64_t wave_chunk_bytes(const rio_ctx* ctx, uint64_t len) {
     return std::min(cb, std::max(want, kSmallFileChunkMin));
 }
 
-// bytes of a file's framing arenas at chunk size cb: scratch (per array) and meta
+// bytes of a file's framing arenas at chunk size cb: scratch (the 16-byte slots) and meta
 struct ArenaSizes {
     uint64_t n_chunks, slots, n_blocks, scratch, meta;
 };
@@ -94,7 +96,7 @@ static ArenaSizes arena_sizes(uint64_t len, uint64_t cb) {
     z.slots = cb / 5 + 1;  // records starting in a chunk: the smallest is v2's 5 bytes
     z.n_blocks = (z.n_chunks + 255) / 256;
     const uint64_t nc = std::max<uint64_t>(z.n_chunks, 1), nb = std::max<uint64_t>(z.n_blocks, 1);
-    z.scratch = nc * z.slots * 8;
+    z.scratch = nc * z.slots * sizeof(WalkSlot);
     auto al = [](uint64_t x) { return (x + 255) & ~255ull; };
     z.meta = al(sizeof(ScanState)) + al(sizeof(rio_file_info)) + 2 * al(nb * sizeof(RunSum)) +
              al(2 * kFailLanes * sizeof(uint64_t)) + al(nc * sizeof(ChunkSum)) + al(nc * sizeof(RunSum)) +
@@ -146,9 +148,7 @@ int rio::ctx_frame_params(rio_ctx* ctx, const uint8_t* d_file, uint64_t len, Fra
             meta_need = std::max(meta_need, y.meta);
         }
     }
-    HIP_TRY(A.scratch_off.ensure(scr));
-    HIP_TRY(A.scratch_len.ensure(scr));
-    HIP_TRY(A.scratch_pay.ensure(scr));
+    HIP_TRY(A.scratch.ensure(scr));
     auto al = [](uint64_t x) { return (x + 255) & ~255ull; };
     const uint64_t o_info = al(sizeof(ScanState)), o_brun = o_info + al(sizeof(rio_file_info));
     const uint64_t o_bexc = o_brun + al(nb * sizeof(RunSum)), o_fail = o_bexc + al(nb * sizeof(RunSum));
@@ -159,9 +159,7 @@ int rio::ctx_frame_params(rio_ctx* ctx, const uint8_t* d_file, uint64_t len, Fra
     uint8_t* const mb = A.meta.as<uint8_t>();
     P.sink = F.sink.as<uint8_t>();
     P.fail_lanes = reinterpret_cast<uint64_t*>(mb + o_fail);
-    P.scratch_off = A.scratch_off.as<uint64_t>();
-    P.scratch_len = A.scratch_len.as<uint64_t>();
-    P.scratch_pay = A.scratch_pay.as<uint64_t>();
+    P.scratch = A.scratch.as<WalkSlot>();
     P.chunks = reinterpret_cast<ChunkSum*>(mb + o_chk);
     P.chunk_excl = reinterpret_cast<RunSum*>(mb + o_cexc);
     P.place = reinterpret_cast<ChunkPlace*>(mb + o_place);
@@ -192,15 +190,18 @@ extern "C" int rio_ctx_create(int device, rio_ctx** out) {
     F.chunk_bytes = env_u64("RIO_CHUNK_BYTES", 32768);
     F.chunk_auto = std::getenv("RIO_CHUNK_BYTES") == nullptr;
     // k_walk's candidate bounds take 32-bit differences inside a chunk (magic_mask): chunks stay below
-    // 1 GiB; anything outside [64, 1 GiB] or not a multiple of 16 falls back to the default
-    if (F.chunk_bytes < 64 || F.chunk_bytes > (1ull << 30) || (F.chunk_bytes & 15)) F.chunk_bytes = 32768;
+    // 1 GiB, and a walked record's slot holds its offset inside its chunk in 30 bits; anything outside
+    // [64, 1 GiB] or not a multiple of 16 falls back to the default
+    static_assert(kMaxChunkBytes == 1ull << 30 && kMaxChunkBytes <= 1ull << kSlotOffBits,
+                  "the chunk cap bounds WalkSlot's chunk-relative offsets and k_walk's 32-bit differences");
+    if (F.chunk_bytes < 64 || F.chunk_bytes > kMaxChunkBytes || (F.chunk_bytes & 15)) F.chunk_bytes = 32768;
     F.walk_mode = (uint32_t)std::min<uint64_t>(env_u64("RIO_WALK_LANE", 2), 2);
     F.lane_chunk_bytes = env_u64("RIO_LANE_CHUNK_BYTES", 16384);
     F.lane_walk_min = env_u64("RIO_LANE_WALK_MIN", kLaneWalkSmallMin);
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
         F.walk_slots = (uint64_t)cus * 4 * kWalkWavesPerSimd;
-    if (F.lane_chunk_bytes < 64 || F.lane_chunk_bytes > (1ull << 30) || (F.lane_chunk_bytes & 15))
+    if (F.lane_chunk_bytes < 64 || F.lane_chunk_bytes > kMaxChunkBytes || (F.lane_chunk_bytes & 15))
         F.lane_chunk_bytes = 16384;
     if (hipHostMalloc(reinterpret_cast<void**>(&F.walk_hint), sizeof(uint64_t), hipHostMallocPortable) != hipSuccess) {
         (void)hipGetLastError();

@@ -72,9 +72,9 @@ struct DevBuf {
 struct FileArenas {
     // meta: the scan state, the file info, the lanes' failure list, the block and chunk summaries and the chunk
     // placements of one call in one allocation (state and block summaries first, 256-byte aligned parts)
-    DevBuf scratch_off, scratch_len, scratch_pay, rec_pay, rec_desc, meta;
+    DevBuf scratch, rec_pay, rec_desc, meta;
     uint64_t bytes() const {
-        return scratch_off.cap + scratch_len.cap + scratch_pay.cap + rec_pay.cap + rec_desc.cap + meta.cap;
+        return scratch.cap + rec_pay.cap + rec_desc.cap + meta.cap;
     }
 };
 

@@ -7,8 +7,14 @@
 
 namespace rio {
 
+#ifdef __HIPCC__
+#define RIO_HD __host__ __device__
+#else
+#define RIO_HD
+#endif
+
 constexpr uint64_t kNone = ~0ull;       // "no speculative entry found in this chunk"
-// scratch_len: decoded length | flag bits
+// WalkSlot::len: decoded length | flag bits
 constexpr uint64_t kNilBit = 1ull << 63;  // nil record
 constexpr uint64_t kBadBit = 1ull << 62;  // payload fails already at framing (codec preamble / size)
 constexpr uint64_t kEofBit = 1ull << 61;  // gzip: empty payload (gzip.NewReader's io.EOF)
@@ -30,6 +36,42 @@ constexpr unsigned kSnappyGrid = RIO_SNAPPY_GRID;
 constexpr unsigned kSnappyGridMax = 1024;
 static_assert(kSnappyGrid <= kSnappyGridMax, "sink sized for kSnappyGridMax workgroups");
 constexpr uint64_t kSinkBytes = (uint64_t)kSnappyBlock / 64 * kSnappyGridMax * 64;
+
+// Framing chunks are at most kMaxChunkBytes long (rio_ctx_create caps RIO_CHUNK_BYTES / RIO_LANE_CHUNK_BYTES there)
+constexpr uint64_t kMaxChunkBytes = 1ull << 30;
+
+// One walked record: 16 bytes, written by the walks with one store and read by k_place with one load.
+//   len: decoded length (bits 0..60) | kEofBit | kBadBit | kNilBit. k_gz_resize / k_lzw_resize rewrite the length.
+//   pos: bits 0..29  record header offset from the chunk's start (a chunk owns the records that start in it, and
+//                    chunks are at most kMaxChunkBytes = 2^30 bytes);
+//        bits 30..37 bytes from the record header start to the first payload byte the decoder consumes (header +
+//                    snappy preamble; the low byte of frame_record's `pay`);
+//        bit  38     escape: the stream length does not fit bits 39..63, which are then 0;
+//        bits 39..63 stream length (the rest of frame_record's `pay`), below kSlotStreamEsc = 32 MiB.
+// The decoded length keeps all of its 61 bits (a resize pass may write any size there), so of the two lengths only
+// the stream length can overflow its field, and the slot takes an escape bit for it (not widths proved against
+// P.len). The decoded length and the flags are always the slot's. k_place recovers an escaped record's stream
+// length from the chain, not by framing the record again (frame_record inside k_place cost it 32 VGPRs, three of
+// its eight waves per SIMD and 256 bytes of scratch per lane): only a record with a payload escapes, for which
+// frame_record gives next = start + header + payload and pay = (payload - k) << 8 | (header + k), so its stream is
+// the bytes from start + (pay & 0xFF) to the chain's next record, and that record's start is in the chunk's next
+// slot or, behind the chunk's last record, in ChunkSum::exit.
+struct alignas(16) WalkSlot {
+    uint64_t len;
+    uint64_t pos;
+};
+constexpr uint32_t kSlotOffBits = 30, kSlotHdrShift = 30, kSlotStreamShift = 39;
+constexpr uint64_t kSlotEsc = 1ull << 38;
+constexpr uint64_t kSlotStreamEsc = 1ull << (64 - kSlotStreamShift);
+// rel = record start - chunk start; len_flags = decoded length | flag bits; pay = frame_record's descriptor
+RIO_HD inline WalkSlot slot_pack(uint64_t rel, uint64_t len_flags, uint64_t pay) {
+    const uint64_t slen = pay >> 8;
+    return WalkSlot{len_flags, rel | (pay & 0xFF) << kSlotHdrShift |
+                                   (slen < kSlotStreamEsc ? slen << kSlotStreamShift : kSlotEsc)};
+}
+RIO_HD inline uint64_t slot_rel(uint64_t pos) { return pos & ((1ull << kSlotOffBits) - 1); }
+// the `pay` descriptor of a slot (with the escape bit: its low byte only)
+RIO_HD inline uint64_t slot_pay(uint64_t pos) { return (pos >> kSlotStreamShift) << 8 | ((pos >> kSlotHdrShift) & 0xFF); }
 
 // Framing chunk: a byte range [cs, ce) of the file; a chunk OWNS the records whose header starts
 // in its range. Written by the walk kernel, consumed by the scan / place kernels.
@@ -111,9 +153,7 @@ struct FrameParams {
     uint64_t chunk_bytes;
     uint64_t n_chunks;
     uint64_t slots;  // scratch slots per chunk
-    uint64_t* scratch_off;   // [n_chunks * slots] record header offsets
-    uint64_t* scratch_len;   // [n_chunks * slots] decoded length | kNilBit
-    uint64_t* scratch_pay;   // [n_chunks * slots] payload descriptor (see rec_pay)
+    WalkSlot* scratch;       // [n_chunks * slots] the walked records of each chunk
     // internal per-record payload descriptor [rec_cap]: bits 0..7 = bytes from the record header
     // start to the first payload byte the decoder consumes (header + snappy preamble), bits 8..63
     // = length of the consumed payload stream (snappy element stream / raw payload). Written for
@@ -374,11 +414,6 @@ struct DbParams {
 
 // protobuf varint length, and proto.Marshal's size of an IndexEntry {key = 1, valueOffset = 2, checksum = 3}:
 // proto3 omits an empty key and zero scalars (sstables/proto/sstable.proto:5-9)
-#ifdef __HIPCC__
-#define RIO_HD __host__ __device__
-#else
-#define RIO_HD
-#endif
 RIO_HD inline uint32_t pb_varint_len(uint64_t v) {
     uint32_t n = 1;
     while (v >= 0x80) {

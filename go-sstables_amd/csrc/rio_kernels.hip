@@ -535,14 +535,24 @@ __device__ uint64_t find_entry(const FrameParams& P, uint64_t cs, uint64_t ce, u
     return kNone;
 }
 
+// A walked record's slot as one 16-byte store / load (x, y = WalkSlot::len, z, w = WalkSlot::pos)
+__device__ __forceinline__ void slot_store(WalkSlot* s, uint64_t rel, uint64_t len_flags, uint64_t pay) {
+    const WalkSlot v = slot_pack(rel, len_flags, pay);
+    *reinterpret_cast<uint4*>(s) =
+        make_uint4((uint32_t)v.len, (uint32_t)(v.len >> 32), (uint32_t)v.pos, (uint32_t)(v.pos >> 32));
+}
+__device__ __forceinline__ WalkSlot slot_load(const WalkSlot* s) {
+    const uint4 v = *reinterpret_cast<const uint4*>(s);
+    return WalkSlot{(uint64_t)v.y << 32 | v.x, (uint64_t)v.w << 32 | v.z};
+}
+
 // Continue walking chunk c from record start p (count/bytes already in s), filling its scratch
-// slots; sets s.exit / s.status. Serial header-to-header hops (FileReader order).
+// slots; sets s.exit / s.status. Serial header-to-header hops (FileReader order). p >= the chunk's start: a
+// speculative entry lies in the chunk, and the repair enters a chunk where the chain left the one before it.
 __device__ void walk_from(const FrameParams& P, uint64_t c, uint64_t p, uint32_t ver, uint32_t comp, ChunkSum& s,
                           const uint32_t* crct = nullptr) {
-    const uint64_t ce = chunk_end(P, c);
-    uint64_t* so = P.scratch_off + c * P.slots;
-    uint64_t* sl = P.scratch_len + c * P.slots;
-    uint64_t* sp = P.scratch_pay + c * P.slots;
+    const uint64_t cs = chunk_start(P, c), ce = chunk_end(P, c);
+    WalkSlot* sc = P.scratch + c * P.slots;
     while (p < ce) {
         Hdr h;
         uint64_t next = 0, olen = 0, pd = 0, lf = 0;
@@ -560,11 +570,7 @@ __device__ void walk_from(const FrameParams& P, uint64_t c, uint64_t p, uint32_t
             }
             break;
         }
-        if (s.count < P.slots) {
-            so[s.count] = p;
-            sl[s.count] = olen | lf | (h.nil ? kNilBit : 0);
-            sp[s.count] = pd;
-        }
+        if (s.count < P.slots) slot_store(sc + s.count, p - cs, olen | lf | (h.nil ? kNilBit : 0), pd);
         s.count++;
         s.bytes += olen;
         p = next;
@@ -783,9 +789,7 @@ __global__ void __launch_bounds__(64 * kWalkWaves) k_walk(FrameParams P) {
     WalkLds& L = W[wv];
     const uint64_t cs = chunk_start(P, c), ce = chunk_end(P, c);
     const uint8_t* f = P.file;
-    uint64_t* so = P.scratch_off + c * P.slots;
-    uint64_t* sl = P.scratch_len + c * P.slots;
-    uint64_t* sp = P.scratch_pay + c * P.slots;
+    WalkSlot* sc = P.scratch + c * P.slots;
     // wave-uniform chain state
     uint64_t p = (c == 0) ? (uint64_t)RIO_FILE_HEADER_BYTES : kNone;  // next record start to chain
     uint32_t mode = (c == 0) ? 1u : 0u;  // 0 entry search, 1 chaining, 2 serial takeover at p
@@ -925,11 +929,7 @@ __global__ void __launch_bounds__(64 * kWalkWaves) k_walk(FrameParams P) {
         }
         // 4. scratch slots of the chained candidates + their decoded bytes
         const uint64_t mylen = slot != ~0u ? ol : 0;
-        if (slot != ~0u && slot < P.slots) {
-            so[slot] = cpos;
-            sl[slot] = ol | lf | (h.nil ? kNilBit : 0);
-            sp[slot] = pd;
-        }
+        if (slot != ~0u && slot < P.slots) slot_store(sc + slot, cpos - cs, ol | lf | (h.nil ? kNilBit : 0), pd);
         uint64_t wsum;
         wave_excl_scan64(mylen, lane, wsum);
         bytes += wsum;
@@ -1033,15 +1033,15 @@ __device__ uint64_t find_entry_lane(const FrameParams& P, uint64_t cs, uint64_t 
 }
 
 // walk_from for one lane: the same records, slots and summary, with the next record's header loads
-// issued before this record's slot stores (on CDNA vmcnt retires loads and stores in issue order: a
-// load issued after the stores would wait for them too), so each hop costs one load round trip.
+// issued before this record's slot store (on CDNA vmcnt retires loads and stores in issue order: a
+// load issued after the store would wait for it too), so each hop costs one load round trip. The slot
+// is one 16-byte store: a wave's lanes write 64 different lines per store instruction, and three 8-byte
+// stores per record were two thirds of the kernel's memory requests.
 __device__ void walk_from_lane(const FrameParams& P, uint64_t c, uint64_t p, uint32_t ver, uint32_t comp, ChunkSum& s,
                                const uint32_t* crct) {
     const uint8_t* f = P.file;
-    const uint64_t ce = chunk_end(P, c);
-    uint64_t* so = P.scratch_off + c * P.slots;
-    uint64_t* sl = P.scratch_len + c * P.slots;
-    uint64_t* sp = P.scratch_pay + c * P.slots;
+    const uint64_t cs = chunk_start(P, c), ce = chunk_end(P, c);
+    WalkSlot* sc = P.scratch + c * P.slots;
     bool have = p < ce && p + 32 <= P.len;
     uint4 a = zero4(), b = zero4();
     if (have) {
@@ -1075,11 +1075,7 @@ __device__ void walk_from_lane(const FrameParams& P, uint64_t c, uint64_t p, uin
             a = ldu16(f + next);
             b = ldu16(f + next + 16);
         }
-        if (s.count < P.slots) {
-            so[s.count] = p;
-            sl[s.count] = olen | lf | (h.nil ? kNilBit : 0);
-            sp[s.count] = pd;
-        }
+        if (s.count < P.slots) slot_store(sc + s.count, p - cs, olen | lf | (h.nil ? kNilBit : 0), pd);
         s.count++;
         s.bytes += olen;
         p = next;
@@ -1440,27 +1436,26 @@ template <uint32_t G>
 __device__ PlaceFlags place_chunk(const FrameParams& P, uint64_t c, uint64_t base_idx, uint64_t base_bytes,
                                   uint64_t owned, bool snappy, bool pay_all, uint32_t lane) {
     PlaceFlags fl{kNone, 0, false, false};
-    const uint64_t* so = P.scratch_off + c * P.slots;
-    const uint64_t* sl = P.scratch_len + c * P.slots;
-    const uint64_t* sp = P.scratch_pay + c * P.slots;
+    const uint64_t cs = chunk_start(P, c);
+    const WalkSlot* sc = P.scratch + c * P.slots;
     bool mixed = false, huge = false;
     uint64_t carry = base_bytes;
-    // scratch of the next 64 records loaded before this step's stores: on CDNA vmcnt retires loads
+    // the slots of the next 64 records loaded before this step's stores: on CDNA vmcnt retires loads
     // and stores in issue order, so a load issued after the stores would wait for them
-    uint64_t l_n = 0, ro_n = 0, pay_n = 0;
-    if (lane < owned) {
-        l_n = sl[lane];
-        ro_n = so[lane];
-        pay_n = sp[lane];
-    }
+    WalkSlot s_n{0, 0};
+    if (lane < owned) s_n = slot_load(sc + lane);
     for (uint64_t k0 = 0; k0 < owned; k0 += G) {
         const uint64_t k = k0 + lane;
         const bool v = k < owned;
-        const uint64_t l = l_n, ro = ro_n, pay = pay_n, len = v ? l & kLenMask : 0;
-        if (k + G < owned) {
-            l_n = sl[k + G];
-            ro_n = so[k + G];
-            pay_n = sp[k + G];
+        const uint64_t l = s_n.len, ro = cs + slot_rel(s_n.pos), len = v ? l & kLenMask : 0;
+        uint64_t pay = slot_pay(s_n.pos);
+        const bool esc = v && (s_n.pos & kSlotEsc);
+        if (k + G < owned) s_n = slot_load(sc + k + G);
+        if (esc) {
+            // an escaped slot (WalkSlot): the stream ends where the chain's next record starts, which is the next
+            // slot's record or, behind the chunk's last record, where the walk left the chunk (ChunkSum::exit)
+            const uint64_t nx = k + 1 < owned ? cs + slot_rel(sc[k + 1].pos) : P.chunks[c].exit;
+            pay |= (nx - ro - pay) << 8;
         }
         uint64_t wsum;
         const uint64_t excl = G == 64 ? wave_excl_scan64(len, lane, wsum) : group16_excl_scan64(len, lane, wsum);

@@ -277,7 +277,7 @@ __global__ void __launch_bounds__(64) k_lzw_resize(FrameParams P) {
     }
     for (uint64_t c = blockIdx.x; c < P.n_chunks; c += gridDim.x) {
         const ChunkPlace pl = P.place[c];
-        uint64_t* sl = P.scratch_len + c * P.slots;
+        WalkSlot* sc = P.scratch + c * P.slots;
         for (uint64_t k = 0; k < pl.owned; k++) {
             const uint64_t i = pl.base_idx + k;
             const uint64_t pay = P.rec_pay[i];
@@ -291,11 +291,11 @@ __global__ void __launch_bounds__(64) k_lzw_resize(FrameParams P) {
                                            nullptr, 0, lane, &total);
             if (lane == 0) {
                 if (rc == kLzOk && total < 0xFFFFFFF0ull) {
-                    const uint64_t old = sl[k] & kLenMask;
-                    sl[k] = (sl[k] & ~kLenMask) | total;
+                    const uint64_t old = sc[k].len & kLenMask;
+                    sc[k].len = (sc[k].len & ~kLenMask) | total;
                     P.chunks[c].bytes += total - old;  // (this wave is the chunk's only writer)
                 } else if (rc == kLzCorrupt) {
-                    sl[k] |= kBadBit;
+                    sc[k].len |= kBadBit;
                 } else {
                     atomicMin((unsigned long long*)&st->unsupported_rec, (unsigned long long)i);
                 }
