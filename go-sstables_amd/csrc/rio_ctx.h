@@ -205,8 +205,9 @@ struct rio_ctx {
     } fl;
 
     // rio_mem_index_build (rio_db_host.cpp): the plan's order and keep flags, the compaction's temp and its count
+    // rio_mem_index_extend: the tail's index, ranks and result block in one allocation (ext); the merged copy
     struct MemIndex {
-        rio::DevBuf src, keep, cub, n_sel;
+        rio::DevBuf src, keep, cub, n_sel, ext, merged;
     } mem;
 
     // rio_wal_ops_plan (rio_tables.cpp): the last plan's segments + record bases, the per-record scratch

@@ -1,9 +1,10 @@
 // rio_db_host.cpp — the entry points of the memstore index and of the combined read (include/rio.h: rio_mem_index_build,
-// rio_mem_lookup, rio_db_*; kernels in rio_memidx.hip and rio_db.hip).
+// rio_mem_index_extend, rio_ops_append, rio_mem_lookup, rio_db_*; kernels in rio_memidx.hip and rio_db.hip).
 //
 // As in rio_super.cpp, all argument checks stand before the first read of *ctx, *reader or of any device state: a
 // call refused on its arguments touches none (tests/test_db_get_host.py makes such calls on a machine without a
-// GPU). rio_mem_index_build sizes its scratch in the call, as the plan it runs does; after rio_db_reader_create no
+// GPU). rio_mem_index_build and rio_mem_index_extend size their scratch in the call, as the plan they run does;
+// rio_ops_append allocates nothing; after rio_db_reader_create no
 // reader call allocates, waits for the device or hands a host array to an asynchronous copy, and rio_mem_lookup
 // never does: the launch parameters travel by value.
 #include <cstring>
@@ -88,6 +89,115 @@ extern "C" int rio_mem_index_build(rio_ctx* ctx, const rio_ops_view* ops, uint32
     P.n_sel = X.n_sel.as<uint64_t>();
     P.result = d_result;
     return hip_status(launch_mem_index(P, X.cub.p, X.cub.cap, rio::stream_of(ctx, stream)));
+}
+
+extern "C" int rio_mem_index_extend(rio_ctx* ctx, const rio_ops_view* ops, uint64_t n_old, uint32_t max_key_len,
+                                    uint64_t* d_order, uint64_t* d_pfx, uint64_t* d_result, void* stream) {
+    if (!ctx || !ops || !d_result) return RIO_ERR_ARG;
+    const uint64_t n = ops->n;
+    if (n_old > n) return RIO_ERR_ARG;
+    if (n && (!ops->keys || !ops->key_off || !ops->values || !ops->val_off || !ops->flags || !d_order || !d_pfx))
+        return RIO_ERR_ARG;
+    if (n >= (1ull << 31) - 1 || max_key_len > RIO_FLUSH_MAX_KEY_LEN) return RIO_ERR_UNSUPPORTED;
+    if (n_old == n) return RIO_OK;
+    if (n_old == 0) return rio_mem_index_build(ctx, ops, max_key_len, d_order, d_pfx, d_result, stream);
+    // from here on *ctx is read
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint64_t t = n - n_old;
+    rio_ctx::MemIndex& X = ctx->mem;
+    HIP_TRY(X.src.ensure(t * 8 + 8));
+    HIP_TRY(X.keep.ensure(t + 8));
+    HIP_TRY(X.n_sel.ensure(8));
+    HIP_TRY(X.cub.ensure(std::max<size_t>(mem_extend_cub_bytes(t), 256)));
+    // ext: the tail's order and prefixes (t words each), lb, eq and e (t + 1 each), its result block, the drop sums
+    HIP_TRY(X.ext.ensure((5 * t + 3 + RIO_MERGE_RESULT_WORDS + 4) * 8));
+    HIP_TRY(X.merged.ensure(2 * n * 8));
+    uint64_t* w = X.ext.as<uint64_t>();
+    uint64_t* b_order = w;
+    uint64_t* b_pfx = b_order + t;
+    uint64_t* lb = b_pfx + t;
+    uint64_t* eq = lb + t + 1;
+    uint64_t* e = eq + t + 1;
+    uint64_t* b_result = e + t + 1;
+    uint64_t* drop = b_result + RIO_MERGE_RESULT_WORDS;
+    // the tail as a log of its own: the offsets are absolute, the arenas the same
+    rio_ops_view tail = *ops;
+    tail.key_off += n_old;
+    tail.val_off += n_old;
+    tail.flags += n_old;
+    tail.n = t;
+    const int rc = flush_plan(ctx, &tail, RIO_FLUSH_WITH_TOMBSTONES, max_key_len, X.src.as<uint64_t>(), X.keep.as<uint8_t>(),
+                              b_result, stream, false);
+    ctx->mrg.planned = false;  // as the build: no gather may follow this plan
+    if (rc != RIO_OK) return rc;
+    hipStream_t s = rio::stream_of(ctx, stream);
+    MemBuildParams B{};
+    B.ops = tail;
+    B.src = X.src.as<uint64_t>();
+    B.keep = X.keep.as<uint8_t>();
+    B.order = b_order;
+    B.pfx = b_pfx;
+    B.n_sel = X.n_sel.as<uint64_t>();
+    B.result = b_result;
+    HIP_TRY(launch_mem_index(B, X.cub.p, X.cub.cap, s));
+    MemExtendParams P{};
+    P.ops = *ops;
+    P.n_old = n_old;
+    P.t = t;
+    P.order = d_order;
+    P.pfx = d_pfx;
+    P.result = d_result;
+    P.b_order = b_order;
+    P.b_pfx = b_pfx;
+    P.b_result = b_result;
+    P.lb = lb;
+    P.eq = eq;
+    P.e = e;
+    P.m_order = X.merged.as<uint64_t>();
+    P.m_pfx = P.m_order + n;
+    P.drop = drop;
+    return hip_status(launch_mem_extend(P, X.cub.p, X.cub.cap, s));
+}
+
+extern "C" int rio_ops_append(rio_ctx* ctx, const rio_ops_view* log, uint64_t ops_cap, uint64_t keys_cap, uint64_t values_cap,
+                              const rio_ops_view* batch, void* stream) {
+    if (!ctx || !log || !batch) return RIO_ERR_ARG;
+    const uint64_t n = batch->n;
+    if (n == 0) return RIO_OK;
+    if (!batch->keys || !batch->key_off || !batch->values || !batch->val_off || !batch->flags || !log->keys || !log->key_off ||
+        !log->values || !log->val_off || !log->flags)
+        return RIO_ERR_ARG;
+    // each sum is checked against a capacity before it can wrap
+    if (log->n > ops_cap || n > ops_cap - log->n) return RIO_ERR_ARG;
+    if (keys_cap < RIO_DEVICE_PAD || log->key_bytes > keys_cap - RIO_DEVICE_PAD ||
+        batch->key_bytes > keys_cap - RIO_DEVICE_PAD - log->key_bytes)
+        return RIO_ERR_ARG;
+    if (values_cap < RIO_DEVICE_PAD || log->value_bytes > values_cap - RIO_DEVICE_PAD ||
+        batch->value_bytes > values_cap - RIO_DEVICE_PAD - log->value_bytes)
+        return RIO_ERR_ARG;
+    if (log->n + n >= (1ull << 31) - 1) return RIO_ERR_UNSUPPORTED;
+    // from here on *ctx is read
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = rio::stream_of(ctx, stream);
+    if (batch->key_bytes)
+        HIP_TRY(hipMemcpyAsync(const_cast<uint8_t*>(log->keys) + log->key_bytes, batch->keys, batch->key_bytes,
+                               hipMemcpyDeviceToDevice, s));
+    if (batch->value_bytes)
+        HIP_TRY(hipMemcpyAsync(const_cast<uint8_t*>(log->values) + log->value_bytes, batch->values, batch->value_bytes,
+                               hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(const_cast<uint8_t*>(log->flags) + log->n, batch->flags, n, hipMemcpyDeviceToDevice, s));
+    OpsRebaseParams P{};
+    P.key_off = const_cast<uint64_t*>(log->key_off);
+    P.val_off = const_cast<uint64_t*>(log->val_off);
+    P.b_key_off = batch->key_off;
+    P.b_val_off = batch->val_off;
+    P.log_n = log->n;
+    P.n = n;
+    P.log_key_bytes = log->key_bytes;
+    P.log_value_bytes = log->value_bytes;
+    P.b_key_bytes = batch->key_bytes;
+    P.b_value_bytes = batch->value_bytes;
+    return hip_status(launch_ops_rebase(P, s));
 }
 
 extern "C" int rio_mem_lookup(rio_ctx* ctx, const rio_mem_index* idx, uint32_t n_idx, const uint8_t* d_keys,

@@ -385,6 +385,33 @@ struct MemBuildParams {
     uint64_t* n_sel;                    // [1] the compaction's count (scratch; the result block's word is read)
     uint64_t* result;                   // [RIO_MERGE_RESULT_WORDS] the plan's, on the device
 };
+// rio_mem_index_extend: A = the index of ops [0, n_old) in order / pfx / result, B = the index of the tail
+// [n_old, ops.n) in context scratch (op words relative to n_old); the merged index returns to order / pfx / result
+struct MemExtendParams {
+    rio_ops_view ops;                   // the whole log
+    uint64_t n_old, t;                  // t = ops.n - n_old > 0
+    uint64_t* order;                    // [ops.n] A, then the merged index
+    uint64_t* pfx;                      // [ops.n]
+    uint64_t* result;                   // [RIO_MERGE_RESULT_WORDS] A's, then the merged index's
+    const uint64_t* b_order;            // [t] B
+    const uint64_t* b_pfx;              // [t]
+    const uint64_t* b_result;           // [RIO_MERGE_RESULT_WORDS] the tail plan's, sealed
+    uint64_t* lb;                       // [t + 1] A keys below B[j]; nA from nB on
+    uint64_t* eq;                       // [t + 1] 1 when A[lb[j]] is B[j]'s key (the scan's input)
+    uint64_t* e;                        // [t + 1] exclusive scan of eq
+    uint64_t* m_order;                  // [ops.n] the merged copy
+    uint64_t* m_pfx;                    // [ops.n]
+    uint64_t* drop;                     // [4] sums over the dropped A entries: count, value bytes, nil values, key bytes
+};
+// rio_ops_append: the offsets of a batch rebased behind a log's
+struct OpsRebaseParams {
+    uint64_t* key_off;                  // the log's, [log_n + n + 1] and more
+    uint64_t* val_off;
+    const uint64_t* b_key_off;          // the batch's, [n + 1]
+    const uint64_t* b_val_off;
+    uint64_t log_n, n;                  // n > 0
+    uint64_t log_key_bytes, log_value_bytes, b_key_bytes, b_value_bytes;
+};
 struct MemLookupParams {
     rio_mem_index i0, i1;               // by value: store 0 and, when n_idx = 2, the newer store 1
     uint32_t n_idx;

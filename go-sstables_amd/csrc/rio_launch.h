@@ -77,6 +77,9 @@ hipError_t launch_flush_plan(const FlushParams& P, hipStream_t s, hipEvent_t* ev
 size_t mem_index_cub_bytes(uint64_t n);
 hipError_t launch_mem_index(const MemBuildParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
 hipError_t launch_mem_lookup(const MemLookupParams& P, hipStream_t s);
+size_t mem_extend_cub_bytes(uint64_t t);
+hipError_t launch_mem_extend(const MemExtendParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
+hipError_t launch_ops_rebase(const OpsRebaseParams& P, hipStream_t s);
 // rio_db.hip
 size_t db_cub_bytes(uint64_t n);
 hipError_t launch_db_value_plan(const DbParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);

@@ -12,8 +12,10 @@ value. Functions return Go-style error values. There is no CPU fallback.
 Batched point reads search the log where it lies on the device: DeviceMemIndex makes an uploaded log searchable
 in place (rio_mem_index_build, csrc/rio_memidx.hip: the flush plan's order compacted to the latest op of every
 key, 16 bytes per distinct key, no key or value copied), MemStore.GetBatch / ContainsBatch answer what loops of
-Get / Contains answer through it. The index is rebuilt, from the log's first op, at the first batched read after
-the log has grown.
+Get / Contains answer through it. At the first batched read after the log has grown, the new ops alone are uploaded
+behind the device copy of the log (DeviceOpLog) and the index is extended by them (rio_mem_index_extend: a sort of
+the new ops and a merge into the old order). DeviceMemStore is the memstore that lives on the device only: batches
+that append_batch left there are appended (rio_ops_append) and indexed without a host copy.
 """
 from __future__ import annotations
 
@@ -96,6 +98,110 @@ def upload_ops(device: int, keys: bytearray, key_off, values: bytearray, val_off
                      max_key_len)
 
 
+class DeviceOpLog:
+    """A growable op log in device memory: the five arrays of rio_ops_view with capacity (key_off / val_off hold
+    ops_cap + 1 words, flags ops_cap bytes, keys keys_cap and values values_cap bytes, the arenas' pad included), and
+    what DeviceOps has: `view` (over the ops so far), `n`, `max_key_len`. append() adds a batch that is on the device
+    (rio_ops_append: two copies device to device and the offsets' rebase, nothing read back); append_host() copies a
+    host tail to its place. Arrays that are too short double, their contents copied device to device."""
+
+    def __init__(self, device: int = 0, ops_cap: int = 1024, keys_cap: int = 1 << 16, values_cap: int = 1 << 16):
+        import torch
+
+        self.device = device
+        self.n = self.key_bytes = self.value_bytes = self.max_key_len = 0
+        self.ops_cap = max(int(ops_cap), 1)
+        self.keys_cap, self.values_cap = (max(int(c), L.RIO_DEVICE_PAD) for c in (keys_cap, values_cap))
+        dev = f"cuda:{device}"
+        with torch.cuda.device(device):
+            self.keys = torch.zeros(self.keys_cap, dtype=torch.uint8, device=dev)
+            self.values = torch.zeros(self.values_cap, dtype=torch.uint8, device=dev)
+            self.key_off = torch.zeros(self.ops_cap + 1, dtype=torch.int64, device=dev)
+            self.val_off = torch.zeros(self.ops_cap + 1, dtype=torch.int64, device=dev)
+            self.flags = torch.zeros(self.ops_cap, dtype=torch.uint8, device=dev)
+
+    @property
+    def view(self):
+        return L.OpsView(keys=self.keys.data_ptr(), key_off=self.key_off.data_ptr(), values=self.values.data_ptr(),
+                         val_off=self.val_off.data_ptr(), flags=self.flags.data_ptr(), n=self.n, key_bytes=self.key_bytes,
+                         value_bytes=self.value_bytes)
+
+    def _reserve(self, n: int, key_bytes: int, value_bytes: int):
+        """Room for n ops, key_bytes and value_bytes in all (and the arenas' pad)."""
+        import torch
+
+        def fit(cap, need):
+            while cap < need:
+                cap *= 2
+            return cap
+
+        def moved(old, size, used):
+            new = torch.zeros(size, dtype=old.dtype, device=old.device)
+            new[:used].copy_(old[:used])
+            return new
+
+        ops_cap = fit(self.ops_cap, n)
+        keys_cap = fit(self.keys_cap, key_bytes + L.RIO_DEVICE_PAD)
+        values_cap = fit(self.values_cap, value_bytes + L.RIO_DEVICE_PAD)
+        if ops_cap != self.ops_cap:
+            self.key_off, self.val_off = moved(self.key_off, ops_cap + 1, self.n + 1), moved(self.val_off, ops_cap + 1, self.n + 1)
+            self.flags = moved(self.flags, ops_cap, self.n)
+        if keys_cap != self.keys_cap:
+            self.keys = moved(self.keys, keys_cap, self.key_bytes)
+        if values_cap != self.values_cap:
+            self.values = moved(self.values, values_cap, self.value_bytes)
+        self.ops_cap, self.keys_cap, self.values_cap = ops_cap, keys_cap, values_cap
+
+    def append(self, batch):
+        """`batch` behind the log: a DeviceOps (what simpledb.append_batch returns), a DeviceOpLog, or a
+        simpledb.WriteBatch, which is uploaded first."""
+        import torch
+
+        from sstables.merger import check_status, on_device_stream
+
+        with torch.cuda.device(self.device):
+            ops = batch.upload(self.device) if hasattr(batch, "upload") else batch
+            bv = ops.view
+            n, kb, vb = int(bv.n), int(bv.key_bytes), int(bv.value_bytes)
+            if n == 0:
+                return self
+            self._reserve(self.n + n, self.key_bytes + kb, self.value_bytes + vb)
+            lv = self.view
+            on_device_stream(self.device, lambda st: check_status(
+                L.lib().rio_ops_append(L.default_ctx(self.device), ctypes.addressof(lv), self.ops_cap, self.keys_cap,
+                                       self.values_cap, ctypes.addressof(bv), st), "rio_ops_append"))
+        self.n, self.key_bytes, self.value_bytes = self.n + n, self.key_bytes + kb, self.value_bytes + vb
+        self.max_key_len = max(self.max_key_len, int(getattr(ops, "max_key_len", L.RIO_FLUSH_MAX_KEY_LEN)))
+        return self
+
+    def append_host(self, keys, key_off, values, val_off, flags):
+        """A host tail behind the log, in upload_ops's shapes (offsets from 0, n + 1 of them). The host knows the
+        log's lengths, so the offsets are rebased here and no kernel runs."""
+        import numpy as np
+        import torch
+
+        n = len(flags)
+        if n == 0:
+            return self
+        ko, vo = np.asarray(key_off, dtype=np.int64), np.asarray(val_off, dtype=np.int64)
+        kb, vb = len(keys), len(values)
+        with torch.cuda.device(self.device):
+            self._reserve(self.n + n, self.key_bytes + kb, self.value_bytes + vb)
+
+            def put(dst, at, arr):
+                if len(arr):
+                    dst[at:at + len(arr)].copy_(torch.from_numpy(arr))
+
+            put(self.keys, self.key_bytes, np.frombuffer(bytearray(keys), dtype=np.uint8))
+            put(self.values, self.value_bytes, np.frombuffer(bytearray(values), dtype=np.uint8))
+            put(self.flags, self.n, np.frombuffer(bytearray(flags), dtype=np.uint8))
+            put(self.key_off, self.n + 1, ko[1:] + self.key_bytes)
+            put(self.val_off, self.n + 1, vo[1:] + self.value_bytes)
+        self.n, self.key_bytes, self.value_bytes = self.n + n, self.key_bytes + kb, self.value_bytes + vb
+        self.max_key_len = max(self.max_key_len, int(np.diff(ko).max()))
+        return self
+
+
 def upload_queries(device: int, keys):
     """Query keys as the arena every lookup takes: (uint8 arena, int64 offsets[n + 1], arena length) on `device`."""
     import numpy as np
@@ -168,16 +274,52 @@ class DeviceMemIndex:
             if self.order is None or n > self.order.numel():
                 self.order = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
                 self.pfx = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-            self.ops, self._rejected = ops, None
+            self.ops, self._rejected, self._n = ops, None, n
             self.err = None
             if ops.max_key_len > L.RIO_FLUSH_MAX_KEY_LEN:  # the device rejects the log too: n_keys = 0
                 self.err = UnsupportedError(f"a key of {ops.max_key_len} bytes: the device orders keys of up to "
                                             f"{L.RIO_FLUSH_MAX_KEY_LEN}")
             bound = min(int(ops.max_key_len), L.RIO_FLUSH_MAX_KEY_LEN)
+            view = ops.view
             on_device_stream(self.device, lambda st: check_status(
-                L.lib().rio_mem_index_build(L.default_ctx(self.device), ctypes.addressof(ops.view), bound,
+                L.lib().rio_mem_index_build(L.default_ctx(self.device), ctypes.addressof(view), bound,
                                             self.order.data_ptr(), self.pfx.data_ptr(), self.result.data_ptr(), st),
                 "rio_mem_index_build"))
+        return self
+
+    def extend(self, ops):
+        """Index `ops`, the SAME log grown longer than at the last rebuild / extend (a DeviceOpLog after append, or a
+        longer DeviceOps over the same ops), from the index as it stands: rio_mem_index_extend sorts the new ops alone
+        and merges them in. order / pfx double while they are too short, their contents kept. A rejection is sticky:
+        only rebuild() clears it."""
+        import torch
+
+        from sstables import UnsupportedError
+        from sstables.merger import check_status, on_device_stream
+
+        n, n_old = int(ops.n), self._n
+        if n < n_old:
+            raise GoError(f"memstore index: a log of {n} ops cannot extend an index of {n_old}")
+        with torch.cuda.device(self.device):
+            if n > self.order.numel():
+                cap = self.order.numel()
+                while cap < n:
+                    cap *= 2
+                for name in ("order", "pfx"):
+                    old = getattr(self, name)
+                    new = torch.empty(cap, dtype=torch.int64, device=old.device)
+                    new[:n_old].copy_(old[:n_old])  # n_keys <= n_old
+                    setattr(self, name, new)
+            self.ops, self._rejected, self._n = ops, None, n
+            if self.err is None and ops.max_key_len > L.RIO_FLUSH_MAX_KEY_LEN:
+                self.err = UnsupportedError(f"a key of {ops.max_key_len} bytes: the device orders keys of up to "
+                                            f"{L.RIO_FLUSH_MAX_KEY_LEN}")
+            bound = min(int(ops.max_key_len), L.RIO_FLUSH_MAX_KEY_LEN)
+            view = ops.view
+            on_device_stream(self.device, lambda st: check_status(
+                L.lib().rio_mem_index_extend(L.default_ctx(self.device), ctypes.addressof(view), n_old, bound,
+                                             self.order.data_ptr(), self.pfx.data_ptr(), self.result.data_ptr(), st),
+                "rio_mem_index_extend"))
         return self
 
     @property
@@ -290,18 +432,25 @@ class MemStore:
         self._key_off, self._val_off = [0], [0]
         self._flags = bytearray()
         self._max_key_len = 0
-        self._idx, self._idx_n = None, -1  # DeviceMemIndex over the uploaded log, and the log length it covers
+        self._idx, self._idx_n = None, -1  # DeviceMemIndex over the device log, and the log length it covers
+        self._dev_log = None               # DeviceOpLog: the ops uploaded so far
 
     def _index(self) -> "DeviceMemIndex":
-        """The device index of the log as it stands: uploaded and rebuilt when the log has grown since."""
-        import torch
+        """The device index of the log as it stands. Only the ops added since the last index are uploaded
+        (DeviceOpLog.append_host) and the index is extended by them (rio_mem_index_extend), whatever their share of
+        the log: DESIGN.md §6 has the extend below the rebuild for every measured tail."""
+        import numpy as np
 
         n = len(self._flags)
         if self._idx is None or self._idx_n != n:
-            with torch.cuda.device(self.device):
-                ops = upload_ops(self.device, self._keys, self._key_off, self._values, self._val_off, self._flags,
-                                 self._max_key_len)
-                self._idx = DeviceMemIndex(ops) if self._idx is None else self._idx.rebuild(ops)
+            if self._dev_log is None:
+                self._dev_log = DeviceOpLog(self.device, ops_cap=max(n, 1024), keys_cap=max(2 * len(self._keys), 1 << 16),
+                                            values_cap=max(2 * len(self._values), 1 << 16))
+            log = self._dev_log
+            a, kb, vb = log.n, log.key_bytes, log.value_bytes
+            log.append_host(self._keys[kb:], np.asarray(self._key_off[a:], dtype=np.int64) - kb, self._values[vb:],
+                            np.asarray(self._val_off[a:], dtype=np.int64) - vb, self._flags[a:])
+            self._idx = DeviceMemIndex(log) if self._idx is None else self._idx.extend(log)
             self._idx_n = n
         return self._idx
 
@@ -409,38 +558,98 @@ class MemStore:
         return bytes(self._keys[self._key_off[op]:self._key_off[op + 1]])
 
     def _flush(self, mode, writer_options):
-        import torch
+        return _flush_log(self.device, lambda: upload_ops(self.device, self._keys, self._key_off, self._values, self._val_off,
+                                                          self._flags, self._max_key_len),
+                          self._max_key_len, mode, writer_options, self._op_key)
 
-        from sstables import UnsupportedError, _WriterOpts, writer_filter
-        from sstables.merger import write_table_files
 
-        o = _WriterOpts()
-        for f in writer_options:
-            f(o)
-        if not o.basePath:
-            return GoError("basePath was not supplied")  # sstable_writer.go:232
-        if o.dataCompressionType not in (L.COMP_NONE, L.COMP_SNAPPY):
-            return UnsupportedError(f"output data compression {o.dataCompressionType}: the device encodes none and snappy")
-        flt, err = writer_filter(o)  # sstable_writer.go:239-241, :78-83
-        if err is not None:
-            return err
-        if self._max_key_len > L.RIO_FLUSH_MAX_KEY_LEN:
-            return UnsupportedError(f"a key of {self._max_key_len} bytes: the device flush orders keys of up to "
-                                    f"{L.RIO_FLUSH_MAX_KEY_LEN}")
-        with torch.cuda.device(self.device):
-            ops = upload_ops(self.device, self._keys, self._key_off, self._values, self._val_off, self._flags,
-                             self._max_key_len)
-            c = flush_ops_on_device(L.default_ctx(self.device), self.device, ops.view, mode, o.dataCompressionType,
-                                    max_key_len=self._max_key_len, flt=flt)
-            if c.status is not None:
-                return GoError(f"memstore flush '{o.basePath}': op {c.unsorted_table} of the log was rejected")
-            lo = hi = b""
-            if c.n_out:
-                first, last = (int(x) & _NONE for x in c.out_src[[0, c.n_out - 1]].cpu().tolist())
-                lo, hi = self._op_key(first), self._op_key(last)
-            write_table_files(o.basePath, c, lo, hi)
-        return None
+def _flush_log(device: int, ops_of, max_key_len: int, mode, writer_options, op_key):
+    """MemStore.Flush / FlushWithTombstones of an op log: the writer options' errors first, then ops_of() (the log on
+    the device: anything with `view`, made under torch.cuda.device(device)) through flush_ops_on_device into the
+    table's three files. op_key(op) -> the key bytes of op, for the table's min / max keys."""
+    import torch
+
+    from sstables import UnsupportedError, _WriterOpts, writer_filter
+    from sstables.merger import write_table_files
+
+    o = _WriterOpts()
+    for f in writer_options:
+        f(o)
+    if not o.basePath:
+        return GoError("basePath was not supplied")  # sstable_writer.go:232
+    if o.dataCompressionType not in (L.COMP_NONE, L.COMP_SNAPPY):
+        return UnsupportedError(f"output data compression {o.dataCompressionType}: the device encodes none and snappy")
+    flt, err = writer_filter(o)  # sstable_writer.go:239-241, :78-83
+    if err is not None:
+        return err
+    if max_key_len > L.RIO_FLUSH_MAX_KEY_LEN:
+        return UnsupportedError(f"a key of {max_key_len} bytes: the device flush orders keys of up to "
+                                f"{L.RIO_FLUSH_MAX_KEY_LEN}")
+    with torch.cuda.device(device):
+        ops = ops_of()
+        view = ops.view
+        c = flush_ops_on_device(L.default_ctx(device), device, view, mode, o.dataCompressionType,
+                                max_key_len=max_key_len, flt=flt)
+        if c.status is not None:
+            return GoError(f"memstore flush '{o.basePath}': op {c.unsorted_table} of the log was rejected")
+        lo = hi = b""
+        if c.n_out:
+            first, last = (int(x) & _NONE for x in c.out_src[[0, c.n_out - 1]].cpu().tolist())
+            lo, hi = op_key(first), op_key(last)
+        write_table_files(o.basePath, c, lo, hi)
+    return None
 
 
 def NewMemStore(device: int = 0) -> MemStore:  # noqa: N802
     return MemStore(device)
+
+
+class DeviceMemStore:
+    """The memstore kept on the device: a DeviceOpLog and the DeviceMemIndex over it. Apply(batch) appends a batch's
+    op log (what simpledb.append_batch returns, without a host copy; a DeviceOpLog; or a simpledb.WriteBatch, which is
+    uploaded) and extends the index by it; the reads are the index's, Size() is its n_keys word, Flush /
+    FlushWithTombstones go through flush_ops_on_device over the log where it lies. There is no host dict: the point
+    calls that need one (Add's KeyAlreadyExists, Delete's KeyNotFound, the size estimate) are MemStore's."""
+
+    def __init__(self, device: int = 0, **caps):
+        self.device = device
+        self.log = DeviceOpLog(device, **caps)
+        self._idx = None
+
+    def Apply(self, batch):  # noqa: N802
+        self.log.append(batch)
+        self._idx = DeviceMemIndex(self.log) if self._idx is None else self._idx.extend(self.log)
+        return None
+
+    def _index(self) -> "DeviceMemIndex":
+        if self._idx is None:
+            self._idx = DeviceMemIndex(self.log)
+        return self._idx
+
+    def GetBatch(self, keys):  # noqa: N802
+        return self._index().GetBatch(keys)
+
+    def ContainsBatch(self, keys):  # noqa: N802
+        return self._index().ContainsBatch(keys)
+
+    def Get(self, key):  # noqa: N802
+        return self._index().Get(key)
+
+    def Contains(self, key) -> bool:  # noqa: N802
+        return self._index().Contains(key)
+
+    def Size(self) -> int:  # noqa: N802
+        """The distinct keys, tombstoned ones included (MemStore.Size): the index's n_keys, read from the device."""
+        return self._index().n_keys()
+
+    def _op_key(self, op: int) -> bytes:
+        a, b = self.log.key_off[op:op + 2].cpu().tolist()
+        return bytes(self.log.keys[a:b].cpu().numpy())
+
+    def Flush(self, *writer_options):  # noqa: N802
+        return _flush_log(self.device, lambda: self.log, self.log.max_key_len, L.RIO_FLUSH_SKIP_TOMBSTONES, writer_options,
+                          self._op_key)
+
+    def FlushWithTombstones(self, *writer_options):  # noqa: N802
+        return _flush_log(self.device, lambda: self.log, self.log.max_key_len, L.RIO_FLUSH_WITH_TOMBSTONES, writer_options,
+                          self._op_key)

@@ -330,6 +330,8 @@ _SIGS = {
     "rio_sst_flush_plan": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rio_sst_flush_stage_ms": (c_int, [c_void_p, POINTER(c_float), c_int]),
     "rio_mem_index_build": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rio_mem_index_extend": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rio_ops_append": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, c_uint64, c_void_p, c_void_p]),
     "rio_mem_lookup": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p]),
     "rio_db_reader_create": (c_int, [c_void_p, c_void_p, c_uint64, POINTER(c_void_p)]),
     "rio_db_reader_free": (None, [c_void_p]),

@@ -439,7 +439,7 @@ class _NoReadStore:
 class DBReadView:
     """DB.GetBytes / Get (db.go:184-242) over `tables` (a sstables.SuperSSTableReader, or None for a database
     without tables yet), the write memstore and the read memstore (the one being flushed, or None). A store is a
-    memstore.MemStore or a memstore.DeviceMemIndex. GetBytes / Get run the reference's host sequence; GetBatch /
+    memstore.MemStore, a memstore.DeviceMemStore or a memstore.DeviceMemIndex. GetBytes / Get run the reference's host sequence; GetBatch /
     GetBatchOnDevice answer a batch on the device. The open / closed checks of db.go:201-207 belong to the DB
     object, which this is not; bytes comparator only."""
 
@@ -490,10 +490,8 @@ class DBReadView:
 
     def _indexes(self):
         """The stores' device indexes, oldest first (the write store last)."""
-        from memstore import MemStore
-
         stores = [s for s in (self.read_store, self.write_store) if s is not None]
-        return [s._index() if isinstance(s, MemStore) else s for s in stores]
+        return [s._index() if hasattr(s, "_index") else s for s in stores]  # a MemStore or a DeviceMemStore
 
     def _host_only(self):
         """The stack's own rule: None, or why its batches are answered on the host."""

@@ -445,6 +445,24 @@ typedef struct rio_ops_view {
     uint64_t key_bytes;        /* length of the key arena: keys are clamped to it */
     uint64_t value_bytes;      /* length of the value arena: values are clamped to it */
 } rio_ops_view;
+/* Grow a device log by a batch's log. `log` is a view over arrays the caller owns, with the given capacities:
+ * key_off and val_off hold ops_cap + 1 words, flags ops_cap bytes, keys keys_cap and values values_cap bytes.
+ * The arrays ARE WRITTEN although the view's pointers are const. The call copies the batch's key bytes behind
+ * log.key_bytes, its value bytes behind log.value_bytes and its flags behind log.n (device to device), and one
+ * kernel (rio_memidx.hip) writes key_off[log.n + 1 + i] = log.key_bytes + min(batch.key_off[i + 1],
+ * batch.key_bytes) for every batch op i, the same for val_off, and key_off[0] = val_off[0] = 0 for log.n = 0.
+ * Afterwards the view with n = log.n + batch.n, key_bytes = log.key_bytes + batch.key_bytes and value_bytes =
+ * log.value_bytes + batch.value_bytes over the same arrays is the log of the old ops followed by the batch's:
+ * the caller computes it, nothing is read back.
+ * Precondition: the batch is as this library's producers leave one, key_off[0] = val_off[0] = 0. Any other batch
+ * gives offsets that stay inside the arenas and a log rio_mem_index_build / _extend accept or reject, never an
+ * out-of-range access.
+ * Stream-ordered (NULL = the ctx stream), never waits for the stream, allocates nothing. batch.n = 0 is a no-op.
+ * Returns RIO_ERR_ARG for a NULL ctx / log / batch, batch.n > 0 with a NULL array on either side, log.n +
+ * batch.n > ops_cap, or new key / value bytes + RIO_DEVICE_PAD above keys_cap / values_cap (the key arena keeps
+ * its readable pad); RIO_ERR_UNSUPPORTED for 2^31 - 1 ops and more in all; before any device call. */
+int rio_ops_append(rio_ctx* ctx, const rio_ops_view* log, uint64_t ops_cap, uint64_t keys_cap, uint64_t values_cap,
+                   const rio_ops_view* batch, void* stream);
 #define RIO_FLUSH_WITH_TOMBSTONES 0u /* FlushWithTombstones: latest op of every key, nil values too */
 #define RIO_FLUSH_SKIP_TOMBSTONES 1u /* Flush: keys whose latest op is nil are left out */
 #define RIO_FLUSH_MAX_KEY_LEN 1024u
@@ -719,7 +737,7 @@ int rio_sst_keys_gather(rio_ctx* ctx, const uint64_t* d_out_src, uint64_t n_out,
  * RIO_ERR_STATE until the next rio_sst_merge_plan / rio_sst_flush_plan); rio_sst_flush_stage_ms reports its
  * stages. Scratch (the plan's, 9 bytes per op and the compaction's temp) is sized in the call, nothing is
  * allocated afterwards. Stream-ordered (NULL = the ctx stream), never waits for the stream. The index costs one
- * sort of the whole log: a log that has grown is indexed again from its first op.
+ * sort of the whole log; a log that has grown is extended from its old index by rio_mem_index_extend.
  * Returns RIO_ERR_ARG for a NULL ctx / ops / d_result or n > 0 with a NULL array, RIO_ERR_UNSUPPORTED for
  * n >= 2^31 - 1 or max_key_len > RIO_FLUSH_MAX_KEY_LEN, before any device call. */
 #define RIO_DB_MAX_MEMSTORES 2u
@@ -731,6 +749,31 @@ typedef struct rio_mem_index {
 } rio_mem_index;
 int rio_mem_index_build(rio_ctx* ctx, const rio_ops_view* ops, uint32_t max_key_len, uint64_t* d_order, uint64_t* d_pfx,
                         uint64_t* d_result, void* stream);
+/* The index of a log that has grown, from the index of its first n_old ops. Precondition: d_order, d_pfx and
+ * d_result hold the index of ops [0, n_old) of this same log, from rio_mem_index_build or an earlier
+ * rio_mem_index_extend, and d_order / d_pfx have room for ops.n words. max_key_len bounds the keys of the new ops
+ * [n_old, ops.n) and sets their sort's pass count. Afterwards the three buffers hold what
+ * rio_mem_index_build(ctx, ops, L, ...) leaves for any L that bounds every key of the log: d_order[0 .. n_keys)
+ * and d_pfx[0 .. n_keys) word for word, and every word of d_result, in the same buffers. n_keys stays in device
+ * memory: nothing is read back, the call never waits for the stream.
+ * The new ops go through the build's stages as a log of their own (sort, keep, compaction, prefixes: cost of a
+ * build over the tail alone); each of their distinct keys is then ranked in the old index by binary search, one
+ * scan counts the old keys the tail rewrote, and old and new entries move to their merged places (16 bytes per op
+ * of scratch) and back. The old ops are not sorted again.
+ * Rejection follows the build's rule, the first rejected op of the whole log: an old index that was rejected
+ * stays rejected with its op; a rejected new op j (a range that leaves its arena or is not monotone, a key longer
+ * than max_key_len) gives RIO_MERGE_R_UNSORTED = n_old + j and n_keys = 0, and nothing else of the index is
+ * meaningful. A rejection is sticky: after it only rio_mem_index_build over the whole log helps.
+ * n_old = ops.n leaves the index as it is; n_old = 0 is the build. A plan call like the build: it replaces the
+ * context's last plan and leaves none. Scratch is sized in the call from ops.n and the tail's length. Every
+ * index read back from a buffer is clamped (the old n_keys to n_old, the tail's to its length, an op to the log,
+ * a position to [0, ops.n)): a wrong input gives a wrong index, never an out-of-range access. A lookup captured
+ * into a hipGraph carries its ops.n by value and clamps n_keys to it: capture the buffers' capacity, as for a
+ * rebuild in place.
+ * Returns RIO_ERR_ARG for n_old > ops.n and what the build refuses, RIO_ERR_UNSUPPORTED as the build, before any
+ * device call. */
+int rio_mem_index_extend(rio_ctx* ctx, const rio_ops_view* ops, uint64_t n_old, uint32_t max_key_len, uint64_t* d_order,
+                         uint64_t* d_pfx, uint64_t* d_result, void* stream);
 /* d_mem_src[i] = store << RIO_MERGE_ENTRY_BITS | op of the newest store of idx[0 .. n_idx) that holds query i =
  * d_keys[d_key_off[i] .. d_key_off[i + 1]), or ~0. Position is age, the highest is the newest (the write store
  * after the read store), as for tables. The first store that holds the key answers, also when its op is nil:

@@ -7,6 +7,11 @@ shared with the next) under a write store of 1M ops over 1M distinct keys in ran
 oldest table's first half, the others keys no table holds; every 16th op a tombstone, the others 1 KiB values.
 index_build   rio_mem_index_build over the log, with the flush plan's stage times (rio_sst_flush_stage_ms: check, the
               length pass, the chunk passes, keep) from one more build with timing on.
+index_extend  the same log with its last 1 Ki, 16 Ki, 128 Ki and 512 Ki ops as the tail, every fourth tail op rewriting a
+              key of the first part: rio_mem_index_extend over the index of the first part against rio_mem_index_build
+              over the whole log, alternated run by run (the old index is restored outside the timed interval); the
+              tail plan's stage times and what follows it (rank, scan, place, copy back) from one more extend with
+              timing on. --only index_extend runs this entry alone, without the tables.
 mem_lookup    rio_mem_lookup alone for three mixes of 1M queries: all in the memstore, none, half; beside each, in the
               same process, rio_sst_lookup (no filter) of the same queries against ONE table that holds the memstore's
               1M keys: the same search without the order indirection.
@@ -58,6 +63,7 @@ def main():
     ap.add_argument("--host-queries", type=int, default=50_000)
     ap.add_argument("--host-keys", type=int, default=20_000)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--only", choices=["index_extend"], default=None, help="run this entry alone (no tables are made)")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args()
 
@@ -96,10 +102,22 @@ def main():
             ms.append(e0.elapsed_time(e1))
         return {"ms": round(sum(ms) / len(ms), 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4)}
 
+    def finish(all_ok):
+        res["verified"] = bool(all_ok)
+        line = json.dumps(res)
+        print(line)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as fh:
+                fh.write(line + "\n")
+        return 0 if all_ok else 1
+
     t0 = time.time()
+    full = args.only is None
     half = n // 2
     n_uni = half * (nt - 1) + n
-    universe = sha_rows(np, 0, n_uni)
+    in_tables = min(n_ops // 2, half * 4 // 5)  # memstore keys the oldest table holds too
+    universe = sha_rows(np, 0, n_uni if full else in_tables)
     values = [np.random.default_rng(1000 + t).integers(0, 256, VALUE_LEN, dtype=np.uint8).tobytes() for t in range(nt)]
     mem_value = np.random.default_rng(999).integers(0, 256, VALUE_LEN, dtype=np.uint8)
     all_ok = True
@@ -117,17 +135,17 @@ def main():
             torch.cuda.synchronize(device)
             return T, tk
 
-        tables = [one_table(universe[t * half:t * half + n], values[t])[0] for t in range(nt)]
-        views = (L.SstView * nt)(*[T["view"] for T in tables])
-        pfx = (ctypes.c_uint64 * nt)(*[T["pfx"].data_ptr() for T in tables])
-        stored = (ctypes.c_uint64 * nt)(*[T["checksum"].data_ptr() for T in tables])
-        stack = ctypes.c_void_p()
-        check(lib.rio_sst_stack_create(ctx, ctypes.addressof(views), ctypes.addressof(pfx), None, ctypes.addressof(stored), nt,
-                                       nq, ctypes.byref(stack), st), "rio_sst_stack_create")
+        if full:
+            tables = [one_table(universe[t * half:t * half + n], values[t])[0] for t in range(nt)]
+            views = (L.SstView * nt)(*[T["view"] for T in tables])
+            pfx = (ctypes.c_uint64 * nt)(*[T["pfx"].data_ptr() for T in tables])
+            stored = (ctypes.c_uint64 * nt)(*[T["checksum"].data_ptr() for T in tables])
+            stack = ctypes.c_void_p()
+            check(lib.rio_sst_stack_create(ctx, ctypes.addressof(views), ctypes.addressof(pfx), None, ctypes.addressof(stored),
+                                           nt, nq, ctypes.byref(stack), st), "rio_sst_stack_create")
 
         # ---- the write store's log: op i holds mem key perm[i]; every 16th op is a tombstone ------------------------
         rng = np.random.default_rng(17)
-        in_tables = min(n_ops // 2, half * 4 // 5)  # memstore keys the oldest table holds too
         mem_rows = np.concatenate([universe[:in_tables], sha_rows(np, 1 << 29, n_ops - in_tables)])
         perm = rng.permutation(n_ops)          # log position -> mem key
         op_of_key = np.empty(n_ops, dtype=np.int64)
@@ -167,6 +185,86 @@ def main():
         res["index_build"] = dict(b_ms, ops=n_ops, distinct_keys=n_ops, ops_per_s=round(n_ops / (b_ms["ms"] / 1e3)),
                                   flush_plan_stage_ms={names[i]: round(stage[i], 4) for i in range(min(k, len(names)))},
                                   equals_model=bool(ok))
+
+        # ---- rio_mem_index_extend against the build of the same final log ------------------------------------------
+        res["index_extend"] = {}
+        log_rows = mem_rows[perm]  # op -> key
+        rng_ext = np.random.default_rng(23)  # its own generator: the later entries' draws stay as they were
+        W = L.RIO_MERGE_RESULT_WORDS
+        old_idx = [torch.empty(n_ops, dtype=torch.int64, device=dev) for _ in range(2)] + [torch.empty(W, dtype=torch.int64, device=dev)]
+        ext_idx = [torch.empty_like(t_) for t_ in old_idx]
+        bld_idx = [torch.empty_like(t_) for t_ in old_idx]
+        for tail in (1 << 10, 1 << 14, 1 << 17, 1 << 19):
+            if tail >= n_ops:
+                continue
+            n_old = n_ops - tail
+            rewrites = np.arange(n_old, n_ops)[::4]  # every fourth tail op writes a key of the first part again
+            rows = log_rows.copy()
+            rows[rewrites] = log_rows[rng_ext.integers(0, n_old, rewrites.shape[0])]
+            d_keys_t = up(np.concatenate([rows.reshape(-1), pad]))
+            whole_log = L.OpsView(keys=d_keys_t.data_ptr(), key_off=d_key_off.data_ptr(), values=d_values.data_ptr(),
+                                  val_off=d_val_off.data_ptr(), flags=d_flags.data_ptr(), n=n_ops, key_bytes=n_ops * KEY_LEN,
+                                  value_bytes=int(val_off[-1]))
+            first_part = L.OpsView(keys=d_keys_t.data_ptr(), key_off=d_key_off.data_ptr(), values=d_values.data_ptr(),
+                                   val_off=d_val_off.data_ptr(), flags=d_flags.data_ptr(), n=n_old, key_bytes=n_old * KEY_LEN,
+                                   value_bytes=int(val_off[n_old]))
+            check(lib.rio_mem_index_build(ctx, ctypes.addressof(first_part), KEY_LEN, old_idx[0].data_ptr(), old_idx[1].data_ptr(),
+                                          old_idx[2].data_ptr(), st), "rio_mem_index_build")
+
+            def extend():
+                check(lib.rio_mem_index_extend(ctx, ctypes.addressof(whole_log), n_old, KEY_LEN, ext_idx[0].data_ptr(),
+                                               ext_idx[1].data_ptr(), ext_idx[2].data_ptr(), st), "rio_mem_index_extend")
+
+            def rebuild():
+                check(lib.rio_mem_index_build(ctx, ctypes.addressof(whole_log), KEY_LEN, bld_idx[0].data_ptr(),
+                                              bld_idx[1].data_ptr(), bld_idx[2].data_ptr(), st), "rio_mem_index_build")
+
+            def pair(ev):
+                for dst, src_ in zip(ext_idx, old_idx):  # the old index again, outside the timed interval
+                    dst.copy_(src_)
+                for call in (extend, rebuild):
+                    ev.append(torch.cuda.Event(enable_timing=True))
+                    ev[-1].record()
+                    call()
+                    ev.append(torch.cuda.Event(enable_timing=True))
+                    ev[-1].record()
+
+            for _ in range(args.warmup):
+                pair([])
+            torch.cuda.synchronize(device)
+            e_ms, r_ms = [], []
+            for _ in range(args.steps):
+                ev = []
+                pair(ev)
+                torch.cuda.synchronize(device)
+                e_ms.append(ev[0].elapsed_time(ev[1]))
+                r_ms.append(ev[2].elapsed_time(ev[3]))
+            words = ext_idx[2].cpu().tolist()
+            nk = words[L.RIO_MERGE_R_N_OUT]
+            ok = (words == bld_idx[2].cpu().tolist() and nk == n_ops - rewrites.shape[0] and words[L.RIO_MERGE_R_UNSORTED] == -1
+                  and torch.equal(ext_idx[0][:nk], bld_idx[0][:nk]) and torch.equal(ext_idx[1][:nk], bld_idx[1][:nk]))
+            all_ok = all_ok and ok
+            # the tail plan's stages and the rest of the call, from one more extend with timing on
+            for dst, src_ in zip(ext_idx, old_idx):
+                dst.copy_(src_)
+            lib.rio_ctx_set_timing(ctx, 1)
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            extend()
+            ev[1].record()
+            torch.cuda.synchronize(device)
+            k = lib.rio_sst_flush_stage_ms(ctx, stage, 16)
+            lib.rio_ctx_set_timing(ctx, 0)
+            plan = {names[i]: round(stage[i], 4) for i in range(min(k, len(names)))}
+            stat = lambda ms: {"ms": round(sum(ms) / len(ms), 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4)}  # noqa: E731
+            res["index_extend"][f"tail_{tail}"] = {
+                "tail_ops": tail, "rewrites": int(rewrites.shape[0]), "old_ops": n_old, "extend": stat(e_ms), "rebuild": stat(r_ms),
+                "extend_over_rebuild": round(sum(e_ms) / sum(r_ms), 4), "tail_plan_stage_ms": plan,
+                "timed_extend_ms": round(ev[0].elapsed_time(ev[1]), 4),
+                "after_plan_ms": round(ev[0].elapsed_time(ev[1]) - sum(stage[i] for i in range(k)), 4), "verified": bool(ok)}
+            del d_keys_t
+        if not full:
+            return finish(all_ok)
 
         index = (L.MemIndex * 1)(L.MemIndex(ops=ops, order=order.data_ptr(), pfx=ipfx.data_ptr(), result=result.data_ptr()))
         # one table of the memstore's keys: the same search without the indirection
@@ -321,14 +419,7 @@ def main():
                                     "get_batch_equals_loop": bool(ok)}
                 view.Close()
 
-    res["verified"] = bool(all_ok)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write(line + "\n")
-    return 0 if all_ok else 1
+    return finish(all_ok)
 
 
 if __name__ == "__main__":
