@@ -66,6 +66,11 @@ constexpr uint64_t kLaneWalkMin = 768, kLaneWalkMax = 8192, kLaneWalkChunks = 32
 // "c2 new" of profiles/r7/r7b_slots_ab.txt), so the class takes it from the same file size as the larger records.
 // Lane chunk: 16 KiB like theirs; 12 KiB framed another 0.010 ms faster with a value inside the run-to-run spread,
 // 8 KiB and 24 KiB slower (lines "lane8k" / "lane12k" / "lane24k" there). RIO_LANE_WALK_MIN overrides kLaneWalkSmallMin.
+// Measured again with the shorter hop of round 15 (lines "new@8192" / "new@12288" / "new@16384" of
+// profiles/r15/r15a_lane_hops_ab.txt, two rounds): C2 464.1 / 467.0 / 470.8 GiB/s; the smaller chunks still walk faster
+// (0.092 / 0.090 / 0.097 ms) and still give it back in the scan, the placement and the decoder, so 16 KiB and these
+// thresholds stay. A chunk that is no power of two (16 656 bytes, the parent build, one run) walked 0.118 against 0.113 ms:
+// the lanes' common 16 KiB stride is not what holds the walk.
 constexpr uint64_t kLaneWalkSmallMin = 512, kLaneWalkSmallChunks = 32768;
 // records of more than kLaneWalkMax bytes on average: wave-walk chunks of at least kBigRecordChunk (a 32 KiB chunk holds
 // at most a few such records and the placement runs a wave per chunk with most lanes idle: C4 place 0.123 -> 0.076 ms,

@@ -354,6 +354,89 @@ __device__ __forceinline__ int frame_fast(const uint32_t (&w)[8], uint64_t len, 
     return kFrameSlow;
 }
 
+// frame_fast in two halves for the lane walk, whose hop waits on one load per record: the lengths (all that the next
+// record's address needs) first, the verification under that load. frame_lengths && frame_verify frames exactly the
+// records frame_fast frames, with the same results; a record that either half refuses takes frame_slow.
+struct FastLen {
+    uint64_t u, c, crc, plen, next;
+    uint32_t nu, nc, hl;  // hl: the whole header, the CRC varint included
+    bool nil;
+};
+// Magic, nil byte, u, c and the length of the CRC varint of the 32 bytes at p (p + 32 <= len). True: L.next is the next
+// record's start and lies in the file (next <= len: plen is compared with the bytes left, never added first, so no
+// length can wrap it).
+__device__ __forceinline__ bool frame_lengths(const uint32_t (&w)[8], uint64_t len, uint64_t p, uint32_t ver, uint32_t comp,
+                                              FastLen& L) {
+    if (!(ver == RIO_VERSION1 ? w[0] == RIO_MAGIC : (w[0] & 0xFFFFFFu) == 0x4C8D91u)) return false;
+    const uint32_t hb = ver >= RIO_VERSION3 ? 4u : 3u;
+    L.u = L.c = L.crc = 0;
+    if (ver == RIO_VERSION1) {
+        L.u = ((uint64_t)w[2] << 32) | w[1];
+        L.c = ((uint64_t)w[4] << 32) | w[3];
+        L.nu = 8;
+        L.nc = 9;  // hb (3) + 8 + 9 = 20
+    } else {
+        L.nu = varint8(win8(w, hb), L.u);
+        L.nc = L.nu ? varint8(win8(w, hb + L.nu), L.c) : 0;
+    }
+    if (!(L.nu && L.nc)) return false;
+    L.hl = hb + L.nu + L.nc;
+    if (ver == RIO_VERSION4) {
+        const uint32_t ncrc = varint8(win8(w, L.hl), L.crc);
+        if (!ncrc) return false;
+        L.hl += ncrc;
+    }
+    L.nil = ver >= RIO_VERSION3 && ((w[0] >> 24) & 0xFF) == 1;
+    L.plen = comp != RIO_COMP_NONE ? L.c : L.u;
+    if (!L.nil) {
+        // snappy: win8 reaches the preamble only while hl <= 20; gzip is sized by its trailer (frame_slow)
+        if (comp == RIO_COMP_SNAPPY ? L.hl > 20 : (comp != RIO_COMP_NONE && comp != RIO_COMP_LZW)) return false;
+        if (L.plen > len - p - L.hl) return false;  // hl < 32 <= len - p
+    }
+    L.next = p + L.hl + (L.nil ? 0 : L.plen);
+    return true;
+}
+// The header CRC-32C, the snappy preamble and its bounds of a record frame_lengths accepted; fills h, out_len, pay.
+__device__ __forceinline__ bool frame_verify(const uint32_t (&w)[8], const FastLen& L, uint32_t ver, uint32_t comp, Hdr& h,
+                                             uint64_t& out_len, uint64_t& pay, const uint32_t* crct) {
+    uint32_t act = 0;
+    if (ver == RIO_VERSION4) {
+        uint32_t cs;
+        if (crct && L.nu + L.nc <= 15) {  // nil byte + both varints: bytes [3, 4 + nu + nc)
+            cs = crc32c_tab(crc_after_magic(), win8(w, 3), win8(w, 11), 1 + L.nu + L.nc, crct);
+        } else {
+            cs = crc32c_byte(crc_after_magic(), (w[0] >> 24) & 0xFF);
+            cs = crc32c_bytes(cs, win8(w, 4), L.nu);
+            cs = crc32c_bytes(cs, win8(w, 4 + L.nu), L.nc);
+        }
+        act = cs ^ 0xFFFFFFFFu;
+        if (act != L.crc) return false;
+    }
+    uint64_t dl = L.plen;
+    uint32_t k = 0;
+    if (!L.nil && comp == RIO_COMP_SNAPPY) {
+        k = varint8(win8(w, L.hl), dl);
+        if (!(k && k <= L.plen && dl <= 0xFFFFFFFFull && dl <= 22ull * (L.plen - k) + 64)) return false;
+    } else if (!L.nil && comp == RIO_COMP_LZW) {
+        dl = lzw_size(L.u, L.plen);
+    }
+    h.u = L.u;
+    h.c = L.c;
+    h.exp_crc = L.crc;
+    h.act_crc = act;
+    h.hdr_len = L.hl;
+    h.magic_len = ver == RIO_VERSION1 ? 0 : 3;
+    h.nil = L.nil;
+    if (L.nil) {  // file_reader.go:96-99: nil => no payload bytes
+        out_len = 0;
+        pay = L.hl;
+    } else {
+        out_len = dl;
+        pay = ((L.plen - k) << 8) | (L.hl + k);
+    }
+    return true;
+}
+
 // The byte-wise path of frame_record (ReadUvarint restatement): every record the fast path does not take,
 // and every failure's exact classification.
 __device__ int frame_slow(const uint8_t* f, uint64_t len, uint64_t p, uint32_t ver, uint32_t comp, Hdr& h,
@@ -968,26 +1051,36 @@ __global__ void __launch_bounds__(64 * kWalkWaves) k_walk(FrameParams P) {
 //   * entry search: 64 bytes per step as four aligned 16-byte loads issued together (plus the next
 //     dword), candidates from magic_mask (0x91 bytes, then the 3-byte test), each framed by
 //     frame_record; the first that frames is the chunk's speculative entry (as find_entry);
-//   * then header to header: each hop is ONE round trip (frame_record's two 16-byte loads, header
-//     parsed in registers, CRC-32C from the LDS slice-by-4 table) and the payload is never read.
+//   * then header to header: each hop is ONE round trip (two 16-byte loads at the header, issued as soon as the
+//     previous header's lengths are known; the header verified in registers under them, CRC-32C from the LDS
+//     slice-by-4 table) and the payload is never read.
 // Slots and ChunkSum are the serial walk's, so the scan, the repair and the placement are unchanged.
 // Against the wave-per-chunk walk (k_walk) it reads ~64 bytes per record instead of every byte, and
-// its framing work is per record, not per candidate window; its cost is one dependent round trip per
-// record per lane, covered by the lanes of ~2 waves per SIMD.
+// its framing work is per record, not per candidate window. Its cost per record per lane is the hop's own
+// instructions at one wave per SIMD (1.9 of 2.2 us on C2) more than the round trip (profiles/r15/r15a_lane_hops_probe.txt).
 // ------------------------------------------------------------------------------------------
-__device__ uint64_t find_entry_lane(const FrameParams& P, uint64_t cs, uint64_t ce, uint32_t ver, uint32_t comp,
-                                    const uint32_t* crct) {
+// A framed record as the walk keeps it: the next record's start and the slot's fields
+struct LaneRec {
+    uint64_t next, olen, pd, lf;
+    bool nil;
+};
+
+// ver / comp: compile-time constants in k_walk_lane's v4 instantiations, the file's values in the generic one. A chunk's
+// entry comes back framed (r), so the walk's first action is the load at r.next.
+__device__ __forceinline__ uint64_t find_entry_lane(const FrameParams& P, uint64_t cs, uint64_t ce, uint32_t ver,
+                                                    uint32_t comp, const uint32_t* crct, LaneRec& r) {
     const uint8_t* f = P.file;
     const uint32_t m3 = magic3(ver);
     // a whole 128-byte line per step (8 loads, the next dword too), the next line loaded before this one's candidates are
     // tested: two steps in flight. Round 6: the entry search was a chain of dependent 64-byte steps, ~3.5 us each under
-    // the walk's load (probe build), C2-ref-random walk 0.129 -> 0.117 ms (profiles/r6/r6r_lane_walk_entry.txt). 16-byte
-    // loads at or past the file end read nothing (the device pad covers 64 bytes only).
+    // the walk's load (probe build), C2-ref-random walk 0.129 -> 0.117 ms (profiles/r6/r6r_lane_walk_entry.txt). The nine
+    // loads go out without a branch each: an address at or past the file end is clamped to the file's last aligned block
+    // (the device pad covers 64 bytes only), whose bytes stand in for positions magic_mask never lists (i + 2 < len - q).
+    const uint64_t last16 = (P.len - 1) & ~15ull, last4 = (P.len - 1) & ~3ull;  // len >= the file header's 8 bytes
     auto fetch = [&](uint64_t q, uint4 (&v)[8], uint32_t& t) __attribute__((always_inline)) {
 #pragma unroll
-        for (uint32_t j = 0; j < 8; j++)
-            v[j] = q + 16 * j < P.len ? *reinterpret_cast<const uint4*>(f + q + 16 * j) : zero4();
-        t = q + 128 < P.len ? *reinterpret_cast<const uint32_t*>(f + q + 128) : 0u;
+        for (uint32_t j = 0; j < 8; j++) v[j] = *reinterpret_cast<const uint4*>(f + umin(q + 16 * j, last16));
+        t = *reinterpret_cast<const uint32_t*>(f + umin(q + 128, last4));
     };
     uint64_t q0 = cs & ~127ull;
     uint4 a[8];
@@ -1020,9 +1113,26 @@ __device__ uint64_t find_entry_lane(const FrameParams& P, uint64_t cs, uint64_t 
                 mlo &= mlo - 1;
             else
                 mhi &= mhi - 1;
+            // frame_record on the candidate, kept framed for the walk. Its 32 bytes are loaded again: taken from the two
+            // lines held by static-index selects (~120 VALU per candidate, the whole wave's) the search was slower, entry
+            // 23.0 -> 26.1 us per lane and C2 walk 0.093 -> 0.097 ms (profiles/r15/r15a_lane_hops_ab.txt, "inreg")
             Hdr hd;
-            uint64_t nxp, ol, pd, lf;
-            if (frame_record(f, P.len, p, ver, comp, hd, nxp, ol, pd, lf, crct) == RIO_OK) return p;
+            int e = kFrameSlow;
+            r.lf = 0;
+            if (p + 32 <= P.len) {
+                const uint4 x = ldu16(f + p), y = ldu16(f + p + 16);
+                const uint32_t w[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+                FastLen L;
+                if (frame_lengths(w, P.len, p, ver, comp, L) && frame_verify(w, L, ver, comp, hd, r.olen, r.pd, crct)) {
+                    r.next = L.next;
+                    e = RIO_OK;
+                }
+            }
+            if (e != RIO_OK) e = frame_slow(f, P.len, p, ver, comp, hd, r.next, r.olen, r.pd, r.lf);
+            if (e == RIO_OK) {
+                r.nil = hd.nil;
+                return p;
+            }
         }
         if (q1 >= ce) return kNone;
         q0 = q1;
@@ -1032,88 +1142,154 @@ __device__ uint64_t find_entry_lane(const FrameParams& P, uint64_t cs, uint64_t 
     }
 }
 
-// walk_from for one lane: the same records, slots and summary, with the next record's header loads
-// issued before this record's slot store (on CDNA vmcnt retires loads and stores in issue order: a
-// load issued after the store would wait for it too), so each hop costs one load round trip. The slot
-// is one 16-byte store: a wave's lanes write 64 different lines per store instruction, and three 8-byte
-// stores per record were two thirds of the kernel's memory requests.
-__device__ void walk_from_lane(const FrameParams& P, uint64_t c, uint64_t p, uint32_t ver, uint32_t comp, ChunkSum& s,
-                               const uint32_t* crct) {
+#if RIO_SCAN_PROBE
+// per lane of k_walk_lane: start, table + header, entry search, end | records; and the part of the hops spent waiting at
+// the header loads (probe build)
+__device__ unsigned long long g_lane[1 << 18][4];
+__device__ unsigned long long g_lane_wait[1 << 18];
+#endif
+// walk_from for one lane: the same records, slots and summary. A hop is one load round trip and nothing else in
+// series with it that the next address does not need: frame_lengths gives the next record's start, the two loads at it
+// go out once it has passed the walk's bounds (next < ce && next + 32 <= len; next <= len by frame_lengths), and the
+// CRC-32C, the snappy preamble and the slot store run under them. A record that then fails frame_verify takes
+// frame_slow exactly as one that fails frame_fast: the loaded bytes are dropped and no slot is stored behind it. The
+// loads precede the slot store (on CDNA vmcnt retires loads and stores in issue order: a load issued after the store
+// would wait for it too). The slot is one 16-byte store: a wave's lanes write 64 different lines per store
+// instruction, and three 8-byte stores per record were two thirds of the kernel's memory requests.
+// framed: the record at p is the entry search's (r), else it is framed here first.
+__device__ __forceinline__ void walk_from_lane(const FrameParams& P, uint64_t c, uint64_t p, bool framed, LaneRec r,
+                                               uint32_t ver, uint32_t comp, ChunkSum& s, const uint32_t* crct) {
     const uint8_t* f = P.file;
     const uint64_t cs = chunk_start(P, c), ce = chunk_end(P, c);
     WalkSlot* sc = P.scratch + c * P.slots;
-    bool have = p < ce && p + 32 <= P.len;
+    bool have = !framed && p < ce && p + 32 <= P.len;
     uint4 a = zero4(), b = zero4();
     if (have) {
         a = ldu16(f + p);
         b = ldu16(f + p + 16);
     }
+#if RIO_SCAN_PROBE
+    unsigned long long twait = 0;
+#endif
     while (p < ce) {
-        Hdr h;
-        uint64_t next = 0, olen = 0, pd = 0, lf = 0;
-        int e = kFrameSlow;
-        if (have) {
-            const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-            e = frame_fast(w, P.len, p, ver, comp, h, next, olen, pd, crct);
-        }
-        if (e != RIO_OK) e = frame_slow(f, P.len, p, ver, comp, h, next, olen, pd, lf);
-        if (e) {
-            s.status = e;
-            s.err_off = p;
-            if (e == RIO_ERR_HEADER_CRC) {
-                s.det0 = h.exp_crc;
-                s.det1 = h.act_crc;
-            } else if (e == RIO_ERR_MAGIC) {
-                s.det0 = h.magic_len;
-            } else if (e == RIO_ERR_UNEXPECTED_EOF && h.hdr_len != 0) {
-                s.det0 = 1;  // raised by the payload read, not by a header varint
+        bool loaded = false;  // the loads at r.next are out (or next is known to have no window)
+        if (!framed) {
+            Hdr h;
+            int e = kFrameSlow;
+            r.lf = 0;
+            if (have) {
+                const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+                FastLen L;
+                if (frame_lengths(w, P.len, p, ver, comp, L)) {
+                    have = L.next < ce && L.next + 32 <= P.len;
+                    if (have) {
+                        a = ldu16(f + L.next);
+                        b = ldu16(f + L.next + 16);
+                    }
+                    if (frame_verify(w, L, ver, comp, h, r.olen, r.pd, crct)) {
+                        r.next = L.next;
+                        loaded = true;
+                        e = RIO_OK;
+                    }
+                }
             }
-            break;
+            if (e != RIO_OK) e = frame_slow(f, P.len, p, ver, comp, h, r.next, r.olen, r.pd, r.lf);
+            if (e) {
+                s.status = e;
+                s.err_off = p;
+                if (e == RIO_ERR_HEADER_CRC) {
+                    s.det0 = h.exp_crc;
+                    s.det1 = h.act_crc;
+                } else if (e == RIO_ERR_MAGIC) {
+                    s.det0 = h.magic_len;
+                } else if (e == RIO_ERR_UNEXPECTED_EOF && h.hdr_len != 0) {
+                    s.det0 = 1;  // raised by the payload read, not by a header varint
+                }
+                break;
+            }
+            r.nil = h.nil;
         }
-        have = next < ce && next + 32 <= P.len;
-        if (have) {
-            a = ldu16(f + next);
-            b = ldu16(f + next + 16);
+        framed = false;
+        if (!loaded) {
+            have = r.next < ce && r.next + 32 <= P.len;
+            if (have) {
+                a = ldu16(f + r.next);
+                b = ldu16(f + r.next + 16);
+            }
         }
-        if (s.count < P.slots) slot_store(sc + s.count, p - cs, olen | lf | (h.nil ? kNilBit : 0), pd);
+        if (s.count < P.slots) slot_store(sc + s.count, p - cs, r.olen | r.lf | (r.nil ? kNilBit : 0), r.pd);
         s.count++;
-        s.bytes += olen;
-        p = next;
+        s.bytes += r.olen;
+        p = r.next;
+#if RIO_SCAN_PROBE
+        {  // what is left of the round trip (and the slot store's) once the record's own work is done
+            const unsigned long long t0 = wall_clock64();
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            twait += wall_clock64() - t0;
+        }
+#endif
     }
     s.exit = s.status ? s.err_off : p;
+#if RIO_SCAN_PROBE
+    if (c < (1u << 18)) g_lane_wait[c] = twait;
+#endif
 }
 
-constexpr uint32_t kWalkLaneBlock = 256;
+// One lane's chunk: entry search, walk, summary
+__device__ __forceinline__ void lane_chunk(const FrameParams& P, uint64_t c, uint32_t ver, uint32_t comp,
+                                           const uint32_t* crct, unsigned long long& tc) {
+    const uint64_t cs = chunk_start(P, c), ce = chunk_end(P, c);
+    LaneRec r{0, 0, 0, 0, false};
+    const uint64_t from = c == 0 ? (uint64_t)RIO_FILE_HEADER_BYTES : find_entry_lane(P, cs, ce, ver, comp, crct, r);
 #if RIO_SCAN_PROBE
-__device__ unsigned long long g_lane[1 << 18][4];
+    tc = wall_clock64();
 #endif
+    ChunkSum s = chunk_sum_empty(from);
+    if (from != kNone) walk_from_lane(P, c, from, c != 0, r, ver, comp, s, crct);
+    P.chunks[c] = s;
+#if RIO_SCAN_PROBE
+    if (c < (1u << 18)) g_lane[c][3] = ((unsigned long long)s.count << 40) | (wall_clock64() & 0xFFFFFFFFFFull);
+#endif
+}
+
+// Lanes per workgroup of k_walk_lane (a multiple of 64; every wave takes its share of the 4 KiB CRC table's copy). 64
+// spreads C2's 535 waves over every CU where 256 holds them on 134 of the 256: C2 walk 0.095 -> 0.089 ms in five of five
+// rounds, but the decode stage behind it measured 0.006 ms longer in the same rounds and the value the same (472.1
+// against 471.6 GiB/s), and C2-ref-random walked 0.095 -> 0.101 ms: 256 stays (profiles/r15/r15a_lane_hops_ab.txt,
+// lines "inreg" = 256 lanes and "wg64").
+#ifndef RIO_LANE_BLOCK
+#define RIO_LANE_BLOCK 256
+#endif
+constexpr uint32_t kWalkLaneBlock = RIO_LANE_BLOCK;
 __global__ void __launch_bounds__(kWalkLaneBlock) k_walk_lane(FrameParams P) {
     __shared__ uint32_t crct[1024];
 #if RIO_SCAN_PROBE
     const unsigned long long ta = wall_clock64();
 #endif
     if (blockIdx.x == 0 && threadIdx.x == 0) init_state(P);
-    crc32c_tab_init(crct);
+    for (uint32_t i = threadIdx.x; i < 256; i += kWalkLaneBlock)
+        reinterpret_cast<uint4*>(crct)[i] = reinterpret_cast<const uint4*>(kCrc32c.t)[i];
+    __syncthreads();
     const uint64_t c = (uint64_t)blockIdx.x * kWalkLaneBlock + threadIdx.x;
     uint32_t ver, comp;
     if (c >= P.n_chunks || file_header_status(P, ver, comp) != RIO_OK) return;
-    const uint64_t cs = chunk_start(P, c), ce = chunk_end(P, c);
+    unsigned long long tc = 0;
 #if RIO_SCAN_PROBE
     const unsigned long long tb = wall_clock64();
 #endif
-    const uint64_t from = c == 0 ? (uint64_t)RIO_FILE_HEADER_BYTES : find_entry_lane(P, cs, ce, ver, comp, crct);
-#if RIO_SCAN_PROBE
-    const unsigned long long tc = wall_clock64();
-#endif
-    ChunkSum s = chunk_sum_empty(from);
-    if (from != kNone) walk_from_lane(P, c, from, ver, comp, s, crct);
-    P.chunks[c] = s;
+    // the file's version and codec are wave-uniform: v4 files without compression and with snappy walk through
+    // instantiations where both are constants, every other file through the generic code
+    if (ver == RIO_VERSION4 && comp == RIO_COMP_NONE)
+        lane_chunk(P, c, RIO_VERSION4, RIO_COMP_NONE, crct, tc);
+    else if (ver == RIO_VERSION4 && comp == RIO_COMP_SNAPPY)
+        lane_chunk(P, c, RIO_VERSION4, RIO_COMP_SNAPPY, crct, tc);
+    else
+        lane_chunk(P, c, ver, comp, crct, tc);
 #if RIO_SCAN_PROBE
     if (c < (1u << 18)) {
         g_lane[c][0] = ta;
         g_lane[c][1] = tb;
         g_lane[c][2] = tc;
-        g_lane[c][3] = ((unsigned long long)s.count << 40) | (wall_clock64() & 0xFFFFFFFFFFull);
     }
 #endif
 }
@@ -1799,7 +1975,7 @@ __global__ void k_probe_dump(uint64_t n_lane, uint64_t n_wave) {
     if (n_lane) {  // the lane walk's per-lane stamps (us): start skew, table + header, entry search, hops, records per lane
         const uint64_t m = n_lane < (1u << 18) ? n_lane : (1u << 18);
         unsigned long long t0 = ~0ull, tend = 0;
-        double sk = 0, s1 = 0, s2 = 0, s3 = 0, cnt = 0, skmax = 0, s2max = 0, s3max = 0;
+        double sk = 0, s1 = 0, s2 = 0, s3 = 0, cnt = 0, skmax = 0, s2max = 0, s3max = 0, wt = 0;
         for (uint64_t c = 0; c < m; c++) t0 = g_lane[c][0] < t0 ? g_lane[c][0] : t0;
         for (uint64_t c = 0; c < m; c++) {
             const unsigned long long a = g_lane[c][0], b = g_lane[c][1], d = g_lane[c][2];
@@ -1809,10 +1985,13 @@ __global__ void k_probe_dump(uint64_t n_lane, uint64_t n_wave) {
             sk += k; s1 += x; s2 += y; s3 += z; cnt += (double)(g_lane[c][3] >> 40);
             skmax = k > skmax ? k : skmax; s2max = y > s2max ? y : s2max; s3max = z > s3max ? z : s3max;
             tend = e2 > tend ? e2 : tend;
+            wt += (double)g_lane_wait[c];
+            g_lane_wait[c] = 0;
         }
         printf("LANE n %llu span %.2f | start skew mean %.2f max %.2f | table+hdr %.2f | entry mean %.2f max %.2f | hops mean %.2f "
-               "max %.2f | records/lane %.2f\n", (unsigned long long)m, (double)(tend - t0) * 0.01, sk / m * 0.01,
-               skmax * 0.01, s1 / m * 0.01, s2 / m * 0.01, s2max * 0.01, s3 / m * 0.01, s3max * 0.01, cnt / m);
+               "max %.2f (at the loads %.2f, the rest %.2f) | records/lane %.2f\n", (unsigned long long)m,
+               (double)(tend - t0) * 0.01, sk / m * 0.01, skmax * 0.01, s1 / m * 0.01, s2 / m * 0.01, s2max * 0.01,
+               s3 / m * 0.01, s3max * 0.01, wt / m * 0.01, (s3 - wt) / m * 0.01, cnt / m);
     }
     const unsigned long long t0 = g_probe[0];
     auto us = [&](int i) { return g_probe[i] >= t0 && g_probe[i] != ~0ull ? (double)(g_probe[i] - t0) * 0.01 : -1.0; };
