@@ -206,8 +206,9 @@ struct rio_ctx {
 
     // rio_mem_index_build (rio_db_host.cpp): the plan's order and keep flags, the compaction's temp and its count
     // rio_mem_index_extend: the tail's index, ranks and result block in one allocation (ext); the merged copy
+    // rio_mem_size_scan: the batch's deltas, the cut word and the batch plan's result block in one allocation (size)
     struct MemIndex {
-        rio::DevBuf src, keep, cub, n_sel, ext, merged;
+        rio::DevBuf src, keep, cub, n_sel, ext, merged, size;
     } mem;
 
     // rio_wal_ops_plan (rio_tables.cpp): the last plan's segments + record bases, the per-record scratch

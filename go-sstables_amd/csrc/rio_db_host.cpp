@@ -1,11 +1,11 @@
 // rio_db_host.cpp — the entry points of the memstore index and of the combined read (include/rio.h: rio_mem_index_build,
-// rio_mem_index_extend, rio_ops_append, rio_mem_lookup, rio_db_*; kernels in rio_memidx.hip and rio_db.hip).
+// rio_mem_index_extend, rio_ops_append, rio_mem_lookup, rio_mem_size_scan, rio_db_*; kernels in rio_memidx.hip,
+// rio_memsize.hip and rio_db.hip).
 //
 // As in rio_super.cpp, all argument checks stand before the first read of *ctx, *reader or of any device state: a
 // call refused on its arguments touches none (tests/test_db_get_host.py makes such calls on a machine without a
-// GPU). rio_mem_index_build and rio_mem_index_extend size their scratch in the call, as the plan they run does;
-// rio_ops_append allocates nothing; after rio_db_reader_create no
-// reader call allocates, waits for the device or hands a host array to an asynchronous copy, and rio_mem_lookup
+// GPU). rio_mem_index_build, rio_mem_index_extend and rio_mem_size_scan size their scratch in the call, as the plan
+// they run does; rio_ops_append allocates nothing; after rio_db_reader_create no reader call allocates, waits for the device or hands a host array to an asynchronous copy, and rio_mem_lookup
 // never does: the launch parameters travel by value.
 #include <cstring>
 
@@ -221,6 +221,48 @@ extern "C" int rio_mem_lookup(rio_ctx* ctx, const rio_mem_index* idx, uint32_t n
     P.key_bytes = key_bytes;
     P.src = d_mem_src;
     return hip_status(launch_mem_lookup(P, rio::stream_of(ctx, stream)));
+}
+
+extern "C" int rio_mem_size_scan(rio_ctx* ctx, const rio_mem_index* store, uint64_t size0, const rio_ops_view* batch,
+                                 uint32_t max_key_len, uint64_t max_size, uint64_t* d_size, uint64_t* d_result,
+                                 void* stream) {
+    if (!ctx || !batch || !d_result) return RIO_ERR_ARG;
+    const uint64_t n = batch->n;
+    if (n && (!batch->keys || !batch->key_off || !batch->values || !batch->val_off || !batch->flags || !d_size))
+        return RIO_ERR_ARG;
+    if (store) {
+        const int rc = check_indexes(store, 1);
+        if (rc != RIO_OK) return rc;
+    }
+    if (n >= (1ull << 31) - 1 || max_key_len > RIO_FLUSH_MAX_KEY_LEN) return RIO_ERR_UNSUPPORTED;
+    // from here on *ctx is read
+    HIP_TRY(hipSetDevice(ctx->device));
+    MemSizeParams P{};
+    if (store) P.store = *store;  // else ops.n = 0: an empty store
+    P.batch = *batch;
+    P.size0 = size0;
+    P.max_size = max_size;
+    P.size = d_size;
+    P.result = d_result;
+    rio_ctx::MemIndex& X = ctx->mem;
+    if (n) {
+        HIP_TRY(X.src.ensure(n * 8 + 8));
+        HIP_TRY(X.keep.ensure(n + 8));
+        // size: the deltas (n words), the cut word, the batch plan's result block
+        HIP_TRY(X.size.ensure((n + 1 + RIO_MERGE_RESULT_WORDS) * 8));
+        HIP_TRY(X.cub.ensure(std::max<size_t>(mem_size_cub_bytes(n), 256)));
+        P.src = X.src.as<uint64_t>();
+        P.keep = X.keep.as<uint8_t>();
+        P.delta = X.size.as<uint64_t>();
+        P.cut = P.delta + n;
+        uint64_t* plan = P.cut + 1;
+        P.plan = plan;
+        const int rc = flush_plan(ctx, batch, RIO_FLUSH_WITH_TOMBSTONES, max_key_len, X.src.as<uint64_t>(), X.keep.as<uint8_t>(),
+                                  plan, stream, false);
+        if (rc != RIO_OK) return rc;
+    }
+    ctx->mrg.planned = false;  // as the index build: no gather may follow this plan
+    return hip_status(launch_mem_size(P, X.cub.p, X.cub.cap, rio::stream_of(ctx, stream)));
 }
 
 extern "C" int rio_db_reader_create(rio_ctx* ctx, rio_sst_stack* stack, uint64_t max_batch, rio_db_reader** out) {

@@ -421,6 +421,19 @@ struct MemLookupParams {
     uint64_t key_bytes;
     uint64_t* src;                      // [n] store << RIO_MERGE_ENTRY_BITS | op, or ~0
 };
+// rio_memsize.hip: the running size estimate of a batch over a write store (rio_mem_size_scan)
+struct MemSizeParams {
+    rio_mem_index store;                // by value; store.ops.n = 0: an empty store
+    rio_ops_view batch;
+    uint64_t size0, max_size;
+    const uint64_t* src;                // [n] the batch plan's order
+    const uint8_t* keep;                // [n] its keep flags
+    const uint64_t* plan;               // [RIO_MERGE_RESULT_WORDS] its result block
+    uint64_t* delta;                    // [n] what op i adds to the size, mod 2^64; size0 rides on op 0
+    uint64_t* size;                     // [n] d_size: the inclusive sum of delta
+    uint64_t* cut;                      // [1] the first over-limit put, or ~0
+    uint64_t* result;                   // [RIO_SIZE_RESULT_WORDS]
+};
 // rio_db.hip: the combined read (rio_db_value_plan / rio_db_value_copy)
 struct DbParams {
     rio_mem_index i0, i1;

@@ -80,6 +80,9 @@ hipError_t launch_mem_lookup(const MemLookupParams& P, hipStream_t s);
 size_t mem_extend_cub_bytes(uint64_t t);
 hipError_t launch_mem_extend(const MemExtendParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
 hipError_t launch_ops_rebase(const OpsRebaseParams& P, hipStream_t s);
+// rio_memsize.hip
+size_t mem_size_cub_bytes(uint64_t n);
+hipError_t launch_mem_size(const MemSizeParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
 // rio_db.hip
 size_t db_cub_bytes(uint64_t n);
 hipError_t launch_db_value_plan(const DbParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);

@@ -57,33 +57,6 @@ namespace {
 // 256 CUs x 8 blocks of 256 lanes: longer batches go round the grid-stride loops again
 constexpr uint64_t kMemGridCap = 2048;
 
-// order[j] of an index, clamped to the log
-__device__ __forceinline__ uint64_t order_at(const rio_mem_index& I, uint64_t j) {
-    const uint64_t op = I.order[j] & kEntryMask;
-    return op < I.ops.n ? op : 0;
-}
-
-// the op of index I that holds q, or ~0
-__device__ __forceinline__ uint64_t find_in_mem(const rio_mem_index& I, const Key& q) {
-    uint64_t lo = 0, hi = mem_n_keys(I);
-    while (lo < hi) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        const uint64_t p = I.pfx[mid];
-        int c;
-        if (p != q.pfx) {
-            c = p < q.pfx ? -1 : 1;
-        } else {
-            const uint64_t op = order_at(I, mid);
-            Key m = op_key(I.ops, op);
-            m.pfx = p;
-            c = key_cmp(m, q);
-            if (c == 0) return op;
-        }
-        if (c < 0) lo = mid + 1; else hi = mid;
-    }
-    return ~0ull;
-}
-
 }  // namespace
 
 __global__ void k_mem_seal(uint64_t* result) {

@@ -1,6 +1,7 @@
 // rio_ops_keys.h — keys and values of an op log on the device (rio_ops_view): the clamped ranges of an op's key and
-// value, and an op's key as the Key the table searches compare (rio_sst_keys.h). Shared by the flush plan
-// (rio_flush.hip), the memstore index and its lookup (rio_memidx.hip) and the combined read (rio_db.hip).
+// value, an op's key as the Key the table searches compare (rio_sst_keys.h), and the binary search of a memstore
+// index for a key. Shared by the flush plan (rio_flush.hip), the memstore index and its lookup (rio_memidx.hip), the
+// size scan (rio_memsize.hip) and the combined read (rio_db.hip).
 // Internal to librio.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -39,6 +40,33 @@ __device__ __forceinline__ Key op_key(const rio_ops_view& o, uint64_t i) {
 // the distinct keys of an index: the build's count read from device memory, clamped to the log's length
 __device__ __forceinline__ uint64_t mem_n_keys(const rio_mem_index& I) {
     return I.ops.n ? umin(I.result[RIO_MERGE_R_N_OUT], I.ops.n) : 0;
+}
+
+// order[j] of an index, clamped to the log
+__device__ __forceinline__ uint64_t order_at(const rio_mem_index& I, uint64_t j) {
+    const uint64_t op = I.order[j] & kEntryMask;
+    return op < I.ops.n ? op : 0;
+}
+
+// the op of index I that holds q, or ~0 (the probe of k_mem_lookup and of k_size_delta)
+__device__ __forceinline__ uint64_t find_in_mem(const rio_mem_index& I, const Key& q) {
+    uint64_t lo = 0, hi = mem_n_keys(I);
+    while (lo < hi) {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        const uint64_t p = I.pfx[mid];
+        int c;
+        if (p != q.pfx) {
+            c = p < q.pfx ? -1 : 1;
+        } else {
+            const uint64_t op = order_at(I, mid);
+            Key m = op_key(I.ops, op);
+            m.pfx = p;
+            c = key_cmp(m, q);
+            if (c == 0) return op;
+        }
+        if (c < 0) lo = mid + 1; else hi = mid;
+    }
+    return ~0ull;
 }
 
 // a memstore source word read back from a buffer: store and op clamped to what exists (false: no such op).

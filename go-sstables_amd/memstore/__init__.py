@@ -15,7 +15,9 @@ key, 16 bytes per distinct key, no key or value copied), MemStore.GetBatch / Con
 Get / Contains answer through it. At the first batched read after the log has grown, the new ops alone are uploaded
 behind the device copy of the log (DeviceOpLog) and the index is extended by them (rio_mem_index_extend: a sort of
 the new ops and a merge into the old order). DeviceMemStore is the memstore that lives on the device only: batches
-that append_batch left there are appended (rio_ops_append) and indexed without a host copy.
+that append_batch left there are appended (rio_ops_append) and indexed without a host copy. Its size estimate comes
+from rio_mem_size_scan (csrc/rio_memsize.hip): the raw estimatedSize after every op of a batch, and the put at which
+db.PutBytes would rotate (ApplyUntilFull).
 """
 from __future__ import annotations
 
@@ -604,22 +606,125 @@ def NewMemStore(device: int = 0) -> MemStore:  # noqa: N802
     return MemStore(device)
 
 
+class SizePlan:
+    """What rio_mem_size_scan found for a batch over a DeviceMemStore (DeviceMemStore.PlanUntilFull): the ops the
+    store takes before db.PutBytes would rotate (`n_applied`; `cut`: whether it rotates after them), the raw size
+    after them and where the batch's arenas split."""
+
+    def __init__(self, ops, n_applied: int, cut: bool, size: int, key_end: int, value_end: int):
+        self.ops, self.n_applied, self.cut = ops, n_applied, cut
+        self.size, self.key_end, self.value_end = size, key_end, value_end
+
+
 class DeviceMemStore:
     """The memstore kept on the device: a DeviceOpLog and the DeviceMemIndex over it. Apply(batch) appends a batch's
     op log (what simpledb.append_batch returns, without a host copy; a DeviceOpLog; or a simpledb.WriteBatch, which is
     uploaded) and extends the index by it; the reads are the index's, Size() is its n_keys word, Flush /
     FlushWithTombstones go through flush_ops_on_device over the log where it lies. There is no host dict: the point
-    calls that need one (Add's KeyAlreadyExists, Delete's KeyNotFound, the size estimate) are MemStore's."""
+    calls that need one (Add's KeyAlreadyExists, Delete's KeyNotFound) are MemStore's. The size estimate is kept
+    without one: rio_mem_size_scan (csrc/rio_memsize.hip) gives the raw estimatedSize after every op of a batch from
+    the index as it stands, so EstimatedSizeInBytes() is what a loop of RWMemstore.Upsert / Delete over every batch
+    so far leaves, and ApplyUntilFull(batch, max_size) stops where db.PutBytes would rotate (db.go:299)."""
 
     def __init__(self, device: int = 0, **caps):
         self.device = device
         self.log = DeviceOpLog(device, **caps)
         self._idx = None
+        self._size = 0            # estimatedSize (raw, before the 1.15 scaling) ...
+        self._size_result = None  # ... or the result block of the last Apply's scan, not read back yet
+
+    def _raw_size(self) -> int:
+        if self._size_result is not None:
+            r, self._size_result = self._size_result, None
+            self._size = int(r[L.RIO_SIZE_R_SIZE].item()) & _NONE
+        return self._size
+
+    def EstimatedSizeInBytes(self) -> int:  # noqa: N802
+        # uint64(1.15 * float32(m.estimatedSize)), as MemStore.EstimatedSizeInBytes
+        return int(_f32(_f32(1.15) * _f32(float(self._raw_size()))))
+
+    def _scan(self, ops, max_size: int):
+        """rio_mem_size_scan of `ops` over the store as it stands -> (d_size, d_result) on the device. Call under
+        torch.cuda.device(self.device), before the ops are appended."""
+        import torch
+
+        from sstables.merger import check_status, on_device_stream
+
+        dev, n = f"cuda:{self.device}", int(ops.view.n)
+        d_size = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        d_result = torch.empty(L.RIO_SIZE_RESULT_WORDS, dtype=torch.int64, device=dev)
+        size0 = self._raw_size()
+        store = None if self._idx is None else self._idx.view
+        bv = ops.view
+        bound = min(int(getattr(ops, "max_key_len", L.RIO_FLUSH_MAX_KEY_LEN)), L.RIO_FLUSH_MAX_KEY_LEN)
+        on_device_stream(self.device, lambda st: check_status(
+            L.lib().rio_mem_size_scan(L.default_ctx(self.device), None if store is None else ctypes.addressof(store), size0,
+                                      ctypes.addressof(bv), bound, max_size & _NONE, d_size.data_ptr(),
+                                      d_result.data_ptr(), st), "rio_mem_size_scan"))
+        return d_size, d_result
+
+    def _append(self, ops):
+        self.log.append(ops)
+        self._idx = DeviceMemIndex(self.log) if self._idx is None else self._idx.extend(self.log)
 
     def Apply(self, batch):  # noqa: N802
-        self.log.append(batch)
-        self._idx = DeviceMemIndex(self.log) if self._idx is None else self._idx.extend(self.log)
+        import torch
+
+        with torch.cuda.device(self.device):
+            ops = batch.upload(self.device) if hasattr(batch, "upload") else batch
+            if int(ops.view.n):  # no cut: the block's SIZE word is the size after the whole batch, read when asked for
+                self._size_result = self._scan(ops, _NONE)[1]
+        self._append(ops)
         return None
+
+    def PlanUntilFull(self, batch, max_size: int):  # noqa: N802
+        """The scan alone -> (SizePlan, err): how many ops of `batch` (a DeviceOps with its tensors, a DeviceOpLog, or a
+        simpledb.WriteBatch, which is uploaded) a loop of db.PutBytes / db.DeleteBytes applies before it rotates a
+        memstore of max_size bytes. The store is not changed; ApplyPlanned(plan) applies those ops. One host read:
+        the scan's 64-byte result block."""
+        import torch
+
+        with torch.cuda.device(self.device):
+            ops = batch.upload(self.device) if hasattr(batch, "upload") else batch
+            n = int(ops.view.n)
+            if n == 0:
+                return SizePlan(ops, 0, False, self._raw_size(), 0, 0), None
+            r = [x & _NONE for x in self._scan(ops, max_size)[1].cpu().tolist()]
+        if r[L.RIO_SIZE_R_FIRST_BAD] != _NONE:
+            return None, GoError(f"memstore size scan: op {r[L.RIO_SIZE_R_FIRST_BAD]} of the batch was rejected")
+        cut = r[L.RIO_SIZE_R_CUT]
+        return SizePlan(ops, n if cut == _NONE else cut + 1, cut != _NONE, r[L.RIO_SIZE_R_SIZE], r[L.RIO_SIZE_R_KEY_END],
+                        r[L.RIO_SIZE_R_VALUE_END]), None
+
+    def ApplyPlanned(self, plan: "SizePlan"):  # noqa: N802
+        """Appends the plan's first n_applied ops (a prefix view of the batch's arrays) and returns the rest of the
+        batch as a DeviceOps, or None: slices of the batch's tensors, the offsets rebased to 0 as rio_ops_append asks."""
+        import torch
+
+        ops, k = plan.ops, plan.n_applied
+        n = int(ops.view.n)
+        if k == 0:
+            return None if n == 0 else ops
+        kb, vb = int(ops.view.key_bytes), int(ops.view.value_bytes)
+        with torch.cuda.device(self.device):
+            head = ops if k == n else DeviceOps(self.device, ops.keys, ops.key_off, ops.values, ops.val_off, ops.flags, k,
+                                                plan.key_end, plan.value_end, ops.max_key_len)
+            self._append(head)
+            self._size, self._size_result = plan.size, None
+            if k == n:
+                return None
+            return DeviceOps(self.device, ops.keys[plan.key_end:], ops.key_off[k:n + 1] - plan.key_end,
+                             ops.values[plan.value_end:], ops.val_off[k:n + 1] - plan.value_end, ops.flags[k:], n - k,
+                             kb - plan.key_end, vb - plan.value_end, ops.max_key_len)
+
+    def ApplyUntilFull(self, batch, max_size: int):  # noqa: N802
+        """Applies the ops of `batch` up to and including the put after which db.PutBytes rotates (db.go:299), or the
+        whole batch -> (n_applied, rest): rest is a DeviceOps over the remaining ops, or None. A batch the device
+        rejects raises its error and leaves the store as it was."""
+        plan, err = self.PlanUntilFull(batch, max_size)
+        if err is not None:
+            raise err
+        return plan.n_applied, self.ApplyPlanned(plan)
 
     def _index(self) -> "DeviceMemIndex":
         if self._idx is None:

@@ -163,6 +163,9 @@ class MemIndex(ctypes.Structure):
     ]
 
 
+RIO_SIZE_RESULT_WORDS = 8  # rio_mem_size_scan's result block
+RIO_SIZE_R_CUT, RIO_SIZE_R_SIZE, RIO_SIZE_R_KEY_END, RIO_SIZE_R_VALUE_END, RIO_SIZE_R_FIRST_BAD = range(5)
+
 RIO_WAL_MAX_SEGMENTS = 4096
 RIO_WAL_RESULT_WORDS = 8
 (RIO_WAL_R_N_RECORDS, RIO_WAL_R_N_OPS, RIO_WAL_R_KEY_BYTES, RIO_WAL_R_VALUE_BYTES, RIO_WAL_R_MAX_KEY_LEN,
@@ -333,6 +336,8 @@ _SIGS = {
     "rio_mem_index_extend": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rio_ops_append": (c_int, [c_void_p, c_void_p, c_uint64, c_uint64, c_uint64, c_void_p, c_void_p]),
     "rio_mem_lookup": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p]),
+    "rio_mem_size_scan": (
+        c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_uint64, c_void_p, c_void_p, c_void_p]),
     "rio_db_reader_create": (c_int, [c_void_p, c_void_p, c_uint64, POINTER(c_void_p)]),
     "rio_db_reader_free": (None, [c_void_p]),
     "rio_db_value_plan": (

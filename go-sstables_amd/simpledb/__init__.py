@@ -16,7 +16,12 @@ The read side is DBReadView: db.GetBytes (db.go:197-242) over a table stack and 
 rw_memstore.go), one key at a time on the host as the reference runs it, and a batch of keys on the device
 (rio_sst_stack_lookup, rio_mem_lookup, rio_db_value_plan / _copy; csrc/rio_memidx.hip, csrc/rio_db.hip). A store
 may be a memstore.DeviceMemIndex: a log that append_batch returned or wal_ops_on_device recovered is read without
-ever having been on the host. There is no DB object (Open / Close, rotation, background flush and compaction).
+ever having been on the host.
+
+The DB object ties them together: NewSimpleDB / Open / Apply / Put / Get / Close (db.go, flush.go,
+recovery.go:117-277). DB.Apply(WriteBatch) leaves what a loop of PutBytes / DeleteBytes leaves: the op at which the
+loop rotates the WAL and the memstore (db.go:299, the size check after every put) comes from rio_mem_size_scan
+(csrc/rio_memsize.hip) over the device memstore. The flush runs inline and compactions do not run.
 Functions return Go-style error values. There is no CPU fallback.
 """
 from __future__ import annotations
@@ -298,23 +303,18 @@ def wal_records_on_device(ctx, device: int, ops_view, mark=None):
     return on_device_stream(device, run)
 
 
-def append_batch(appender, batch, device: int = 0, mark=None):
-    """The WAL half of a loop of db.PutBytes / db.DeleteBytes over `batch` (a WriteBatch, or a
-    memstore.DeviceOps that is on the device already): upload, rio_wal_ops_encode, rio_device_encode with
-    the appender's writer's compression, the image and its offsets to the host, wal.Appender.AppendFramed.
-    The directory is what the host loop of proto.marshal_upsert / marshal_delete + Append leaves. Returns
-    (ops, err): ops is the memstore.DeviceOps, whose view memstore.flush_ops_on_device takes as it is."""
+def wal_image_on_device(batch, comp: int, device: int = 0, mark=None):
+    """The part of append_batch before the write: upload, rio_wal_ops_encode, rio_device_encode with compression
+    `comp` (none or snappy), the image and its offsets to the host. `batch` is a WriteBatch, a memstore.DeviceOps
+    or an OpsView whose arrays the caller keeps alive. Returns (ops, framed, err): ops is the memstore.DeviceOps;
+    framed is None for an empty batch, else (image, out_rec_off, raw_len) as wal.Appender.AppendFramed takes them
+    (a v4 file image of every op's WalMutation record, each record's offset in it, each record's length before
+    framing)."""
     import torch
 
-    from recordio.writer import FileWriter
-    from sstables import UnsupportedError
     from sstables.merger import check_status, on_device_stream
 
     mark = mark or (lambda name: None)
-    w = appender.currentWriter
-    if not isinstance(w, FileWriter) or w.compression not in (L.COMP_NONE, L.COMP_SNAPPY):
-        return None, UnsupportedError("append_batch writes through a recordio.FileWriter with compression none or snappy")
-    comp = w.compression
     lib, dev = L.lib(), f"cuda:{device}"
     with torch.cuda.device(device):
         ctx = L.default_ctx(device)
@@ -327,10 +327,10 @@ def append_batch(appender, batch, device: int = 0, mark=None):
         mark("upload")
         n = int(ops.view.n)
         if n == 0:
-            return ops, None
+            return ops, None, None
         records, rec_off, r = wal_records_on_device(ctx, device, ops.view, mark)
         if r[L.RIO_WALENC_R_FIRST_BAD] != _NONE:
-            return ops, GoError(f"append batch: op {r[L.RIO_WALENC_R_FIRST_BAD]} of the log was rejected")
+            return ops, None, GoError(f"append batch: op {r[L.RIO_WALENC_R_FIRST_BAD]} of the log was rejected")
         total = r[L.RIO_WALENC_R_BYTES]
         cap = int(lib.rio_encode_bound(n, total, comp))
 
@@ -347,8 +347,26 @@ def append_batch(appender, batch, device: int = 0, mark=None):
             return image, offs, raw
 
         image, offs, raw = on_device_stream(device, run)
-    err = appender.AppendFramed(image, offs, raw[1:] - raw[:-1])
-    return ops, err
+    return ops, (image, offs, raw[1:] - raw[:-1]), None
+
+
+def append_batch(appender, batch, device: int = 0, mark=None):
+    """The WAL half of a loop of db.PutBytes / db.DeleteBytes over `batch` (a WriteBatch, or a
+    memstore.DeviceOps that is on the device already): upload, rio_wal_ops_encode, rio_device_encode with
+    the appender's writer's compression, the image and its offsets to the host (wal_image_on_device),
+    wal.Appender.AppendFramed. The directory is what the host loop of proto.marshal_upsert / marshal_delete +
+    Append leaves. Returns (ops, err): ops is the memstore.DeviceOps, whose view memstore.flush_ops_on_device
+    takes as it is."""
+    from recordio.writer import FileWriter
+    from sstables import UnsupportedError
+
+    w = appender.currentWriter
+    if not isinstance(w, FileWriter) or w.compression not in (L.COMP_NONE, L.COMP_SNAPPY):
+        return None, UnsupportedError("append_batch writes through a recordio.FileWriter with compression none or snappy")
+    ops, framed, err = wal_image_on_device(batch, w.compression, device, mark)
+    if err is not None or framed is None:
+        return ops, err
+    return ops, appender.AppendFramed(*framed)
 
 
 def _reset_dir(base_path: str):
@@ -608,3 +626,298 @@ class DBReadView:
                     else:
                         out.append((None, ErrNotFound))
             return out
+
+
+# ---- the DB object (db.go, flush.go, recovery.go:117-277) ---------------------------------------------------------
+
+SSTablePrefix = "sstable"  # db.go:20-25
+SSTablePattern = SSTablePrefix + "_%015d"
+SSTableCompactionPathPrefix = SSTablePrefix + "_compaction"
+WriteAheadFolder = "wal"
+MemStoreMaxSizeBytes = 1024 * 1024 * 1024
+
+ErrNotOpenedYet = GoError("database has not been opened yet, please call Open() first")  # db.go:34-36
+ErrAlreadyOpen = GoError("database is already open")
+ErrAlreadyClosed = GoError("database is already closed")
+
+
+class ExtraOptions:
+    """db.go:414-425, the fields this DB reads; `device` is not in the reference."""
+
+    def __init__(self):
+        self.memstoreSizeBytes = MemStoreMaxSizeBytes
+        self.enableCompactions = True
+        self.device = 0
+
+
+def MemstoreSizeBytes(n: int):  # noqa: N802
+    """db.go:431: the size of the memstore after which it is written to disk."""
+    def f(o): o.memstoreSizeBytes = n
+    return f
+
+
+def DisableCompactions():  # noqa: N802
+    """db.go:438. Compactions do not run here whatever this says."""
+    def f(o): o.enableCompactions = False
+    return f
+
+
+def OnDevice(device: int):  # noqa: N802
+    """Not in the reference: the GPU that holds the memstore and the tables."""
+    def f(o): o.device = device
+    return f
+
+
+class DB:
+    """simpledb.DB (db.go:81-347) with the write path batched: Apply(WriteBatch) leaves the directory and the reads
+    that a loop of PutBytes / DeleteBytes over the batch leaves, rotations included. The memstore is a
+    memstore.DeviceMemStore, the WAL records are marshalled and framed on the device (wal_image_on_device), and the
+    op at which the loop would rotate comes from rio_mem_size_scan (DeviceMemStore.PlanUntilFull), once per
+    segment. The flush runs inline in the writing call (flush.go's goroutine is not mirrored: there is never a read
+    store, and a failed flush is returned); compactions do not run; one writer at a time, there is no lock."""
+
+    def __init__(self, basePath: str, opts: ExtraOptions):  # noqa: N803
+        self.basePath = basePath
+        self.memstoreMaxSize = int(opts.memstoreSizeBytes)
+        self.enableCompactions = opts.enableCompactions
+        self.device = opts.device
+        self.currentGeneration = 0
+        self.open = self.closed = False
+        self.wal = None       # the wal.Appender
+        self.readers = []     # sstableManager.allSSTableReaders, oldest first
+        self.tables = None    # the SuperSSTableReader over them, None without a table
+        self.memStore = None  # the write store
+        self.view = None      # DBReadView over tables and memStore
+
+    # ---- Open / Close ---------------------------------------------------------------------------------------------
+
+    def _table_dirs(self):
+        """reconstructSSTables' walk (recovery.go:120-130): every directory under basePath, itself included, whose
+        name starts with SSTablePrefix; sorted."""
+        def onerror(e):
+            raise e
+
+        out = []
+        for root, _, _ in os.walk(self.basePath, onerror=onerror):
+            if os.path.basename(root).startswith(SSTablePrefix):
+                out.append(root)
+        return sorted(out)
+
+    def _restack(self):
+        """A new stack over the readers and a new read view over it and the write store."""
+        from sstables import NewSuperSSTableReader
+
+        if self.view is not None:
+            self.view.Close()
+        if self.tables is not None:
+            self.tables._free_stack()
+        self.tables = NewSuperSSTableReader(self.readers) if self.readers else None
+        self.view = DBReadView(self.tables, self.memStore)
+
+    def _add_table(self, path: str):
+        from sstables import NewSSTableReader, ReadBasePath, ReadOnDevice
+
+        reader, err = NewSSTableReader(ReadBasePath(path), ReadOnDevice(self.device))
+        if err is None:
+            self.readers.append(reader)
+        return err
+
+    def Open(self):  # noqa: N802
+        from memstore import DeviceMemStore
+        from recordio.writer import NewFileWriter
+        from sstables import UnsupportedError
+        from wal import BasePath, MaximumWalFileSizeBytes, NewAppender, NewWriteAheadLogOptions, WriterFactory
+
+        if self.open:
+            return ErrAlreadyOpen
+        try:
+            paths = self._table_dirs()
+        except OSError as e:
+            return GoError(str(e))
+        for p in paths:  # repairCompactions' and the compactor's directories: such a database stays with the reference
+            if os.path.basename(p).startswith(SSTableCompactionPathPrefix):
+                return UnsupportedError(f"'{p}': a database with a compaction directory is opened by the reference")
+        # reconstructSSTables
+        for p in paths:
+            suffix = os.path.basename(p)[len(SSTablePrefix) + 1:]
+            if not (suffix.isascii() and suffix.isdigit()) or int(suffix) >= 1 << 64:
+                return GoError(f'strconv.ParseUint: parsing "{suffix}": invalid syntax')
+            err = self._add_table(p)
+            if err is not None:
+                return err
+            self.currentGeneration = max(self.currentGeneration, int(suffix))
+        # replayAndSetupWriteAheadLog: the replay flushes into the next generation (executeFlush) when it held an op
+        wal_base = os.path.join(self.basePath, WriteAheadFolder)
+        try:
+            os.makedirs(wal_base, mode=0o700, exist_ok=True)
+        except OSError as e:
+            return GoError(f"could not mkdir WAL dir at {wal_base}: {e}")
+        table = os.path.join(self.basePath, SSTablePattern % (self.currentGeneration + 1))
+        _, wrote, err = recover_wal(wal_base, table, device=self.device, bloom_filter=True)
+        if err is not None:
+            return err
+        if wrote:
+            self.currentGeneration += 1
+            err = self._add_table(table)
+            if err is not None:
+                return err
+        # we rotate in lockstep with the memstore flushes: the size limit is set far above them (recovery.go:193-195)
+        o, err = NewWriteAheadLogOptions(BasePath(wal_base), MaximumWalFileSizeBytes(self.memstoreMaxSize * 100),
+                                         WriterFactory(lambda path: NewFileWriter(path, L.COMP_SNAPPY)))
+        if err is not None:
+            return err
+        self.wal, err = NewAppender(o)
+        if err is not None:
+            return err
+        self.memStore = DeviceMemStore(self.device)
+        self._restack()
+        self.open = True
+        return None
+
+    def _check(self):
+        if not self.open:
+            return ErrNotOpenedYet
+        if self.closed:
+            return ErrAlreadyClosed
+        return None
+
+    def Close(self):  # noqa: N802
+        """db.go:150-187: the last rotation and flush, then the WAL (its fresh, header-only file stays) and the
+        readers."""
+        err = self._check()
+        if err is not None:
+            return err
+        self.closed = True
+        err = self._rotate_wal_and_flush_memstore()
+        if err is not None:
+            return err
+        errs = [self.wal.Close(), self.view.Close(), None if self.tables is None else self.tables.Close()]
+        errs = [e for e in errs if e is not None]
+        return GoError("\n".join(str(e) for e in errs)) if errs else None
+
+    # ---- writes -----------------------------------------------------------------------------------------------------
+
+    def _rotate_wal_and_flush_memstore(self):
+        """rotateWalAndFlushMemstore and executeFlush (flush.go:32-108), inline."""
+        from memstore import DeviceMemStore
+        from sstables import BloomExpectedNumberOfElements, EnableBloomFilter, WriteBasePath
+
+        wal_path, err = self.wal.Rotate()
+        if err is not None:
+            return err
+        store = self.memStore
+        if store.log.n == 0:  # nothing to write: the WAL file stays (flush.go:37-40); the empty store serves on
+            return None
+        self.memStore = DeviceMemStore(self.device)
+        gen = self.currentGeneration = self.currentGeneration + 1
+        path = os.path.join(self.basePath, SSTablePattern % gen)
+        try:
+            os.makedirs(path, mode=0o700, exist_ok=True)
+        except OSError as e:
+            return GoError(str(e))
+        err = store.FlushWithTombstones(WriteBasePath(path), EnableBloomFilter(), BloomExpectedNumberOfElements(store.Size()))
+        if err is not None:
+            return err
+        try:
+            os.remove(wal_path)
+        except OSError as e:
+            return GoError(str(e))
+        err = self._add_table(path)
+        if err is not None:
+            return err
+        self._restack()
+        return None
+
+    def Apply(self, batch: "WriteBatch"):  # noqa: N802
+        """What a loop of PutBytes / DeleteBytes over the batch leaves: per op the WAL record, the memstore op and,
+        after a put, the size check and the rotation (db.go:256-347). Per segment (the ops up to and including the
+        put that rotates): the segment's framed records to the WAL, its ops to the memstore, the rotation."""
+        from sstables import UnsupportedError
+
+        err = self._check()
+        if err is not None:
+            return err
+        n = len(batch)
+        if n == 0:
+            return None
+        if batch._max_key_len > L.RIO_FLUSH_MAX_KEY_LEN:  # before anything is written
+            return UnsupportedError(f"a key of {batch._max_key_len} bytes: the device orders keys of up to "
+                                    f"{L.RIO_FLUSH_MAX_KEY_LEN}")
+        ops, framed, err = wal_image_on_device(batch, self.wal.currentWriter.compression, self.device)
+        if err is not None:
+            return err
+        image, offs, raw = framed
+        a = 0
+        while ops is not None:
+            plan, err = self.memStore.PlanUntilFull(ops, self.memstoreMaxSize)
+            if err is not None:
+                return err
+            b = a + plan.n_applied
+            err = self.wal.AppendFramed(image if b == n else image[:int(offs[b])], offs[a:b], raw[a:b])
+            if err is not None:
+                return err
+            ops = self.memStore.ApplyPlanned(plan)
+            if plan.cut:
+                err = self._rotate_wal_and_flush_memstore()
+                if err is not None:
+                    return err
+            a = b
+        return None
+
+    def PutBytes(self, key, value):  # noqa: N802
+        b = WriteBatch()
+        b.PutBytes(key, value)
+        return self.Apply(b)
+
+    def DeleteBytes(self, key):  # noqa: N802
+        b = WriteBatch()
+        b.DeleteBytes(key)
+        return self.Apply(b)
+
+    def Put(self, key: str, value: str):  # noqa: N802
+        if len(key) == 0 or len(value) == 0:
+            return ErrEmptyKeyValue
+        return self.PutBytes(key.encode(), value.encode())
+
+    def Delete(self, key: str):  # noqa: N802
+        return self.DeleteBytes(key.encode())
+
+    # ---- reads ------------------------------------------------------------------------------------------------------
+
+    def GetBytes(self, key):  # noqa: N802
+        err = self._check()
+        if err is not None:
+            return None, err
+        return self.view.GetBytes(key)
+
+    def Get(self, key: str):  # noqa: N802
+        err = self._check()
+        if err is not None:
+            return "", err
+        return self.view.Get(key)
+
+    def GetBatch(self, keys):  # noqa: N802
+        """[(value, err)] per key, equal to a loop of GetBytes."""
+        err = self._check()
+        if err is not None:
+            return [(None, err) for _ in keys]
+        return self.view.GetBatch(keys)
+
+    def GetBatchOnDevice(self, d_keys, d_key_off, n: int):  # noqa: N802
+        """DBReadView.GetBatchOnDevice over the current tables and write store; raises the open / closed error."""
+        err = self._check()
+        if err is not None:
+            raise err
+        return self.view.GetBatchOnDevice(d_keys, d_key_off, n)
+
+
+def NewSimpleDB(basePath: str, *extraOptions):  # noqa: N802,N803
+    """db.go:351-410: the directory must exist -> (DB, err)."""
+    try:
+        os.listdir(basePath)
+    except OSError as e:
+        return None, GoError(f"open {basePath}: {(e.strerror or str(e)).lower()}")
+    o = ExtraOptions()
+    for f in extraOptions:
+        f(o)
+    return DB(basePath, o), None

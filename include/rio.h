@@ -787,6 +787,43 @@ int rio_mem_index_extend(rio_ctx* ctx, const rio_ops_view* ops, uint64_t n_old, 
  * n >= 2^31 - 1 or an index of 2^40 ops and more. n = 0 is a no-op. */
 int rio_mem_lookup(rio_ctx* ctx, const rio_mem_index* idx, uint32_t n_idx, const uint8_t* d_keys,
                    const uint64_t* d_key_off, uint64_t n, uint64_t key_bytes, uint64_t* d_mem_src, void* stream);
+/* The write store's size estimate after every op of a batch, and the op at which a loop of db.PutBytes /
+ * db.DeleteBytes would rotate (simpledb/db.go:299: EstimatedSizeInBytes() > memstoreMaxSize after every put, no
+ * check after a delete, db.go:311-347). store = the write store's index as rio_mem_lookup takes it (NULL or
+ * ops.n = 0: an empty store), size0 = its raw estimatedSize (memstore.go:32, before the 1.15 scaling), batch = a
+ * batch as WriteBatch.upload leaves it (offsets from 0). d_size[i] (batch->n words) = the raw estimatedSize after
+ * op i: what a loop of RWMemstore.Upsert / RWMemstore.Delete over ops 0 .. i leaves (memstore.go:119-178,
+ * rw_memstore.go:48-63) when the write store started in store's state with size0; arithmetic mod 2^64 as Go's
+ * uint64. d_result is a block of RIO_SIZE_RESULT_WORDS words in DEVICE memory:
+ *   RIO_SIZE_R_CUT        the first op i that is a put (not nil) with uint64(1.15 * float32(d_size[i])) > max_size,
+ *                         or ~0. The expression is Go's (memstore.go:182): the u64 -> f32 conversion rounds to
+ *                         nearest, one float32 multiply by float32(1.15), truncation; a product of 2^64 and more
+ *                         counts as 2^64 - 1
+ *   RIO_SIZE_R_SIZE       d_size[CUT]; d_size[n - 1] without a cut; size0 for n = 0
+ *   RIO_SIZE_R_KEY_END    key_off[CUT + 1] (key_off[n] without a cut, 0 for n = 0): where the batch's key arena splits
+ *   RIO_SIZE_R_VALUE_END  val_off[CUT + 1], the same for the value arena
+ *   RIO_SIZE_R_FIRST_BAD  the first batch op the flush plan's check rejects (a range that leaves its arena or is
+ *                         not monotone, a key longer than max_key_len), or ~0; 0 for a store index that was
+ *                         rejected (its RIO_MERGE_R_UNSORTED set). Nothing else in the block or in d_size is
+ *                         meaningful then
+ * The batch goes through the flush plan's check, sort and keep stages under RIO_FLUSH_WITH_TOMBSTONES; an op's
+ * predecessor is its neighbour in that order or, for the first op of a key, the store's entry found by
+ * rio_mem_lookup's binary search; one inclusive sum gives the sizes, one pass the cut. It is a plan call like
+ * rio_mem_index_build: it REPLACES the context's last plan and leaves none. Scratch (the plan's, 17 bytes per op,
+ * the scan's temp) is sized in the call from the context's arenas. Stream-ordered (NULL = the ctx stream), never
+ * waits for the stream. Every index read back from a buffer is clamped (an op to its log, n_keys to the store's
+ * ops.n, ranges to their arenas): a wrong input gives wrong words, never an out-of-range access.
+ * Returns RIO_ERR_ARG for a NULL ctx / batch / d_result, n > 0 with a NULL array or a NULL d_size, a store refused
+ * as by rio_mem_lookup; RIO_ERR_UNSUPPORTED for n >= 2^31 - 1 or max_key_len > RIO_FLUSH_MAX_KEY_LEN, before any
+ * device call. n = 0 writes the result block only. */
+#define RIO_SIZE_RESULT_WORDS 8u
+#define RIO_SIZE_R_CUT 0u
+#define RIO_SIZE_R_SIZE 1u
+#define RIO_SIZE_R_KEY_END 2u
+#define RIO_SIZE_R_VALUE_END 3u
+#define RIO_SIZE_R_FIRST_BAD 4u
+int rio_mem_size_scan(rio_ctx* ctx, const rio_mem_index* store, uint64_t size0, const rio_ops_view* batch,
+                      uint32_t max_key_len, uint64_t max_size, uint64_t* d_size, uint64_t* d_result, void* stream);
 /* The combined read. A reader owns the scan's scratch for batches of up to max_batch queries (8 bytes per query
  * and the scan's temp); stack = NULL is a database without tables yet. The stack must outlive the reader. After
  * create no reader call allocates, waits for the device or reads a host array.
