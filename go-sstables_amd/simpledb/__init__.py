@@ -21,14 +21,21 @@ ever having been on the host.
 The DB object ties them together: NewSimpleDB / Open / Apply / Put / Get / Close (db.go, flush.go,
 recovery.go:117-277). DB.Apply(WriteBatch) leaves what a loop of PutBytes / DeleteBytes leaves: the op at which the
 loop rotates the WAL and the memstore (db.go:299, the size check after every put) comes from rio_mem_size_scan
-(csrc/rio_memsize.hip) over the device memstore. The flush runs inline and compactions do not run.
-Functions return Go-style error values. There is no CPU fallback.
+(csrc/rio_memsize.hip) over the device memstore. The flush runs inline.
+
+Compaction (compaction.go, sstable_manager.go, recovery.go:22-114) is opt-in, CompactOnDevice(): the selection
+(candidate_tables_for_compaction) and the crash-safe directory protocol (repair_compactions, the compaction_successful
+record) are host functions that need no GPU; the merge is SSTableMerger.MergeCompact over the DB's own resident readers,
+and the compacted table enters the stack from the buffers the merge left in HBM (sstables._DeviceTable.from_compaction),
+without reading its files back. Functions return Go-style error values. There is no CPU fallback.
 """
 from __future__ import annotations
 
 import ctypes
 import os
 import shutil
+import struct
+import tempfile
 import types
 
 from recordio import _lib as L
@@ -633,8 +640,12 @@ class DBReadView:
 SSTablePrefix = "sstable"  # db.go:20-25
 SSTablePattern = SSTablePrefix + "_%015d"
 SSTableCompactionPathPrefix = SSTablePrefix + "_compaction"
+CompactionFinishedSuccessfulFileName = "compaction_successful"
 WriteAheadFolder = "wal"
 MemStoreMaxSizeBytes = 1024 * 1024 * 1024
+NumSSTablesToTriggerCompaction = 10
+DefaultCompactionMaxSizeBytes = 5 * 1024 * 1024 * 1024
+DefaultCompactionRatio = struct.unpack("f", struct.pack("f", 0.2))[0]  # float32(0.2)
 
 ErrNotOpenedYet = GoError("database has not been opened yet, please call Open() first")  # db.go:34-36
 ErrAlreadyOpen = GoError("database is already open")
@@ -647,6 +658,11 @@ class ExtraOptions:
     def __init__(self):
         self.memstoreSizeBytes = MemStoreMaxSizeBytes
         self.enableCompactions = True
+        self.compactionFileThreshold = NumSSTablesToTriggerCompaction
+        self.compactionMaxSizeBytes = DefaultCompactionMaxSizeBytes
+        self.compactionRatio = DefaultCompactionRatio
+        self.compactionRunInterval = 5.0  # accepted and unused: a pass runs where a table is added, not on a ticker
+        self.compactOnDevice = False
         self.device = 0
 
 
@@ -657,9 +673,208 @@ def MemstoreSizeBytes(n: int):  # noqa: N802
 
 
 def DisableCompactions():  # noqa: N802
-    """db.go:438. Compactions do not run here whatever this says."""
+    """db.go:438. Compactions run only under CompactOnDevice(), and not when this was passed too."""
     def f(o): o.enableCompactions = False
     return f
+
+
+def CompactOnDevice():  # noqa: N802
+    """Not in the reference: the opt-in to compactions. Without it a database with a compaction directory stays with
+    the reference (Open returns UnsupportedError) and no compaction runs."""
+    def f(o): o.compactOnDevice = True
+    return f
+
+
+def CompactionRunInterval(seconds: float):  # noqa: N802
+    """db.go:458: accepted and ignored, there is no ticker here."""
+    def f(o): o.compactionRunInterval = seconds
+    return f
+
+
+def CompactionRatio(ratio: float):  # noqa: N802
+    """db.go:472: the share of tombstones from which a table is a candidate whatever its size; float32."""
+    if not 0.0 <= ratio <= 1.0:  # a NaN too; Go panics
+        raise ValueError("invalid compaction ratio: %f, must be between 0 and 1" % ratio)
+    def f(o): o.compactionRatio = struct.unpack("f", struct.pack("f", ratio))[0]
+    return f
+
+
+def CompactionFileThreshold(n: int):  # noqa: N802
+    """db.go:483: a pass compacts only more candidates than this."""
+    def f(o): o.compactionFileThreshold = n
+    return f
+
+
+def CompactionMaxSizeBytes(n: int):  # noqa: N802
+    """db.go:492: a table of fewer totalBytes than this is a candidate."""
+    def f(o): o.compactionMaxSizeBytes = n
+    return f
+
+
+# ---- compaction, the parts that need no GPU (sstable_manager.go:115-185, compaction.go:148-172, recovery.go:22-114) ----
+
+def _u64_to_f32(n: int) -> float:
+    """Go's float32(uint64): round to nearest, ties to even, on the integer (a double in between rounds twice)."""
+    if n < 1 << 24:
+        return float(n)
+    shift = n.bit_length() - 24
+    q, r, half = n >> shift, n & ((1 << shift) - 1), 1 << (shift - 1)
+    if r > half or (r == half and q & 1):
+        q += 1
+    return float(q << shift)
+
+
+def flood_fill(a):
+    """floodFill (sstable_manager.go:158-185): the values enclosed by true values become true as well."""
+    a = list(a)
+    sel = [i for i, x in enumerate(a) if x]
+    if sel:
+        a[sel[0]:sel[-1] + 1] = [True] * (sel[-1] + 1 - sel[0])
+    return a
+
+
+def candidate_tables_for_compaction(tables, compaction_max_size_bytes: int, compaction_ratio: float):
+    """candidateTablesForCompaction (sstable_manager.go:115-156) over `tables` = [(base path, MetaData)], oldest first
+    -> (the selected paths, the sum of their numRecords). A table is selected below the size limit, or (when it holds a
+    record) from the tombstone ratio on, float32(nullValues) / float32(numRecords) >= ratio as Go computes it; the
+    gaps between selected tables are filled so that the lineage is kept."""
+    ratio = struct.unpack("f", struct.pack("f", compaction_ratio))[0]
+    selected = []
+    for _, m in tables:
+        s = m.totalBytes < compaction_max_size_bytes
+        if m.numRecords > 0:
+            # the double quotient of two float32 values, rounded to float32, is the float32 quotient
+            q = struct.unpack("f", struct.pack("f", _u64_to_f32(m.nullValues) / _u64_to_f32(m.numRecords)))[0]
+            s = s or q >= ratio
+        selected.append(s)
+    selected = flood_fill(selected)
+    paths = [p for (p, _), s in zip(tables, selected) if s]
+    return paths, sum(m.numRecords for (_, m), s in zip(tables, selected) if s)
+
+
+def save_compaction_metadata(write_folder: str, m):
+    """saveCompactionMetadata (compaction.go:148-172): the one marshalled record in a recordio file with the writer's
+    defaults (the current version, uncompressed) -> err."""
+    from recordio.writer import NewFileWriter
+
+    try:
+        record = proto.marshal_compaction_metadata(m)
+    except ValueError as e:
+        return GoError(_PROTO_PREFIX + str(e))
+    w, err = NewFileWriter(os.path.join(write_folder, CompactionFinishedSuccessfulFileName), L.COMP_NONE)
+    if err is None:
+        err = w.Open()
+    if err is not None:
+        return err
+    _, err = w.Write(record)
+    cerr = w.Close()
+    return err or cerr
+
+
+def _crc32c(b: bytes) -> int:
+    c = 0xFFFFFFFF
+    for x in b:
+        c ^= x
+        for _ in range(8):
+            c = (c >> 1) ^ (0x82F63B78 & -(c & 1))
+    return c ^ 0xFFFFFFFF
+
+
+def _first_record_on_host(img: bytes):
+    """The first record of a recordio file image in the writer's default form (version 4, uncompressed), read on the
+    host: readRecordHeaderV4 (common_reader.go:110-151) and the payload. None for a nil record; raises ValueError for
+    anything the reader would refuse, a file without a record included."""
+    from sstables.proto import _varint
+
+    pos = 8
+    if pos >= len(img):
+        raise ValueError("EOF")
+    magic, pos = _varint(img, pos)
+    if magic != 0x130691:
+        raise ValueError("magic number mismatch")
+    if pos >= len(img):
+        raise ValueError("unexpected EOF")
+    nil, pos = img[pos], pos + 1
+    size, pos = _varint(img, pos)
+    _, pos = _varint(img, pos)
+    actual = _crc32c(img[8:pos])
+    expected, pos = _varint(img, pos)
+    if actual != expected:
+        raise ValueError("header checksum mismatch")
+    if size > len(img) - pos:
+        raise ValueError("unexpected EOF")
+    return None if nil == 1 else img[pos:pos + size]
+
+
+def read_compaction_metadata(path: str):
+    """The CompactionMetadata of a compaction_successful file -> (metadata, err). The file as saveCompactionMetadata
+    writes it is read on the host, so that repair_compactions needs no GPU: recordio.reader decodes on the device.
+    A file of another version or with a compression goes through recordio.reader."""
+    try:
+        with open(path, "rb") as fh:
+            img = fh.read()
+    except OSError as e:
+        return None, GoError(str(e))
+    try:
+        if len(img) >= 8 and img[:8] == struct.pack("<II", 4, L.COMP_NONE):
+            record = _first_record_on_host(img)
+        else:
+            from recordio.reader import NewFileReaderWithPath
+
+            r, err = NewFileReaderWithPath(path)
+            if err is None:
+                err = r.Open()
+            if err is not None:
+                return None, err
+            record, err = r.ReadNext()
+            r.Close()
+            if err is not None:
+                return None, err
+        return proto.unmarshal_compaction_metadata(record), None
+    except ValueError as e:  # the wire format's and the UTF-8 error too
+        return None, GoError(str(e))
+
+
+def repair_compactions(base_path: str):
+    """repairCompactions (recovery.go:22-114) -> err. Every directory under base_path whose name starts with
+    SSTableCompactionPathPrefix: without a readable metadata record it is deleted (the compaction can be attempted
+    again); with one the compaction is finished: the replacement path removed, the write folder renamed to it, the
+    other inputs removed. Needs no GPU."""
+    to_finish, to_delete = [], []
+
+    def onerror(e):
+        raise e
+
+    try:
+        for root, _, _ in os.walk(base_path, onerror=onerror):
+            if os.path.basename(root).startswith(SSTableCompactionPathPrefix):
+                m, err = read_compaction_metadata(os.path.join(root, CompactionFinishedSuccessfulFileName))
+                if err is not None:
+                    to_delete.append(root)
+                else:
+                    to_finish.append(m)
+        for p in to_delete:
+            _remove_all(p)
+        for m in to_finish:
+            write_path, replacement = os.path.join(base_path, m.writePath), os.path.join(base_path, m.replacementPath)
+            _remove_all(replacement)
+            os.rename(write_path, replacement)
+            for p in m.sstablePaths:
+                if p != m.replacementPath:
+                    _remove_all(os.path.join(base_path, p))
+    except OSError as e:
+        return GoError(str(e))
+    return None
+
+
+def _remove_all(path: str):
+    """os.RemoveAll: a path that does not exist is no error."""
+    try:
+        shutil.rmtree(path)
+    except FileNotFoundError:
+        pass
+    except NotADirectoryError:
+        os.remove(path)
 
 
 def OnDevice(device: int):  # noqa: N802
@@ -674,12 +889,21 @@ class DB:
     memstore.DeviceMemStore, the WAL records are marshalled and framed on the device (wal_image_on_device), and the
     op at which the loop would rotate comes from rio_mem_size_scan (DeviceMemStore.PlanUntilFull), once per
     segment. The flush runs inline in the writing call (flush.go's goroutine is not mirrored: there is never a read
-    store, and a failed flush is returned); compactions do not run; one writer at a time, there is no lock."""
+    store, and a failed flush is returned); one writer at a time, there is no lock. Under CompactOnDevice() one
+    compaction pass (executeCompaction + reflectCompactionResult, one tick of the reference's ticker) runs inline at
+    the end of Open and after every rotation that added a table, and on demand (Compact); its error is returned by the
+    call that triggered it."""
 
     def __init__(self, basePath: str, opts: ExtraOptions):  # noqa: N803
         self.basePath = basePath
         self.memstoreMaxSize = int(opts.memstoreSizeBytes)
         self.enableCompactions = opts.enableCompactions
+        self.compactOnDevice = opts.compactOnDevice
+        self.compactionFileThreshold = int(opts.compactionFileThreshold)
+        self.compactedMaxSizeBytes = int(opts.compactionMaxSizeBytes)
+        self.compactionRatio = opts.compactionRatio
+        self.installCompactedFromDevice = True  # False: reflect reloads the compacted table from its files
+        self._compacted = None  # (write path, the merge's Compaction) between execute and reflect
         self.device = opts.device
         self.currentGeneration = 0
         self.open = self.closed = False
@@ -730,6 +954,10 @@ class DB:
 
         if self.open:
             return ErrAlreadyOpen
+        if self._compaction_active():  # db.go:122: before the tables are reconstructed
+            err = repair_compactions(self.basePath)
+            if err is not None:
+                return err
         try:
             paths = self._table_dirs()
         except OSError as e:
@@ -772,7 +1000,8 @@ class DB:
         self.memStore = DeviceMemStore(self.device)
         self._restack()
         self.open = True
-        return None
+        _, err = self._compaction_pass()
+        return err
 
     def _check(self):
         if not self.open:
@@ -788,7 +1017,7 @@ class DB:
         if err is not None:
             return err
         self.closed = True
-        err = self._rotate_wal_and_flush_memstore()
+        err = self._rotate_wal_and_flush_memstore(compact=False)
         if err is not None:
             return err
         errs = [self.wal.Close(), self.view.Close(), None if self.tables is None else self.tables.Close()]
@@ -797,8 +1026,9 @@ class DB:
 
     # ---- writes -----------------------------------------------------------------------------------------------------
 
-    def _rotate_wal_and_flush_memstore(self):
-        """rotateWalAndFlushMemstore and executeFlush (flush.go:32-108), inline."""
+    def _rotate_wal_and_flush_memstore(self, compact: bool = True):
+        """rotateWalAndFlushMemstore and executeFlush (flush.go:32-108), inline. compact: a compaction pass follows a
+        rotation that added a table (Close passes False: the reference stops its ticker before the last flush)."""
         from memstore import DeviceMemStore
         from sstables import BloomExpectedNumberOfElements, EnableBloomFilter, WriteBasePath
 
@@ -826,7 +1056,131 @@ class DB:
         if err is not None:
             return err
         self._restack()
+        if compact:
+            _, err = self._compaction_pass()
+            return err
         return None
+
+    # ---- compaction (compaction.go:57-146, sstable_manager.go:24-85) ----------------------------------------------
+
+    def _compaction_active(self) -> bool:
+        return self.compactOnDevice and self.enableCompactions
+
+    def _index_of_reader(self, name: str) -> int:
+        for i, r in enumerate(self.readers):
+            if os.path.basename(r.BasePath()) == name:
+                return i
+        return -1
+
+    def _execute_compaction(self):
+        """executeCompaction (compaction.go:57-146) -> (CompactionMetadata or None when nothing was compacted, err).
+        The inputs are the DB's own readers, resident in HBM; the table is written into a fresh write folder with its
+        compaction_successful record. On an error the write folder is removed."""
+        from sstables import (BloomExpectedNumberOfElements, EnableBloomFilter, NewSSTableMerger,
+                              ScanReduceLatestWinsSkipTombstones, _WriterOpts)
+
+        paths, num_records = candidate_tables_for_compaction([(r.BasePath(), r.MetaData()) for r in self.readers],
+                                                             self.compactedMaxSizeBytes, self.compactionRatio)
+        if len(paths) <= self.compactionFileThreshold:
+            return None, None
+        paths.sort()  # make sure we're always compacting with the right order in mind (compaction.go:65)
+        try:
+            write_folder = tempfile.mkdtemp(prefix=SSTableCompactionPathPrefix, dir=self.basePath)
+        except OSError as e:
+            return None, GoError(str(e))
+        by_path = {r.BasePath(): r for r in self.readers}
+        merger = NewSSTableMerger(data_compression=_WriterOpts().dataCompressionType)  # the flush's
+        try:
+            err = merger.MergeCompact([by_path[p] for p in paths], write_folder, ScanReduceLatestWinsSkipTombstones,
+                                      writer_options=(EnableBloomFilter(), BloomExpectedNumberOfElements(num_records)))
+        except OSError as e:
+            err = GoError(str(e))
+        except GoError as e:
+            err = e
+        names = [os.path.basename(p) for p in paths]  # relative to the base path, to be portable (compaction.go:125)
+        m = proto.CompactionMetadata(writePath=os.path.basename(write_folder), replacementPath=names[0], sstablePaths=names)
+        if err is None:
+            err = save_compaction_metadata(write_folder, m)
+        if err is not None:
+            shutil.rmtree(write_folder, ignore_errors=True)
+            return None, err
+        self._compacted = (m.writePath, merger.compaction)
+        return m, None
+
+    def _reflect_compaction_result(self, m):
+        """reflectCompactionResult (sstable_manager.go:24-85) -> err: the inputs' directories go, the write folder takes
+        the replacement's name, the new reader takes the replacement's place in the readers and the other inputs leave
+        them. The new reader is made from the buffers the merge left in HBM when they are at hand (a metadata that
+        _execute_compaction has just returned) and reads no file; else the table is loaded from its files."""
+        import torch
+
+        from sstables import NewSSTableReader, ReadBasePath, ReadOnDevice, SSTableReader, _DeviceTable, _Opts
+
+        replacement = os.path.join(self.basePath, m.replacementPath)
+        held, self._compacted = self._compacted, None
+        reader = None
+        if self.installCompactedFromDevice and held is not None and held[0] == m.writePath:
+            c = held[1]
+            try:
+                with torch.cuda.device(self.device):
+                    t = _DeviceTable.from_compaction(replacement, self.device, c, c.data_file, c.index_file)
+            except GoError as e:
+                return e
+            reader = SSTableReader(_Opts(basePath=replacement, device=self.device), c.meta, t, c.filter)
+        del held
+        i = self._index_of_reader(m.replacementPath)
+        if i < 0:
+            return GoError(f"couldn't find replacement sstable in current readers. Path: {m.replacementPath}")
+        others = [p for p in m.sstablePaths if p != m.replacementPath]
+        gone = [self._index_of_reader(p) for p in others]
+        for p, k in zip(others, gone):
+            if k < 0:
+                return GoError(f"couldn't find sstable in current readers. Path: {p}")
+        try:
+            for p in m.sstablePaths:
+                if self._index_of_reader(p) >= 0:
+                    _remove_all(os.path.join(self.basePath, p))
+            os.rename(os.path.join(self.basePath, m.writePath), replacement)
+        except OSError as e:
+            return GoError(str(e))
+        if reader is None:
+            reader, err = NewSSTableReader(ReadBasePath(replacement), ReadOnDevice(self.device))
+            if err is not None:
+                return err
+        old = [self.readers[k] for k in [i] + gone]
+        readers = list(self.readers)
+        readers[i] = reader
+        self.readers = [r for k, r in enumerate(readers) if k not in gone]
+        self._restack()  # the old stack's views go before the tables they point into
+        for r in old:
+            r.Close()
+        return None
+
+    def _compaction_pass(self):
+        """One tick of backgroundCompaction (compaction.go:32-46) -> (metadata or None, err); nothing when compaction
+        is not active."""
+        if not self._compaction_active():
+            return None, None
+        m, err = self._execute_compaction()
+        if err is not None or m is None:
+            return None, err
+        err = self._reflect_compaction_result(m)
+        if err is not None:
+            shutil.rmtree(os.path.join(self.basePath, m.writePath), ignore_errors=True)
+            return None, err
+        return m, None
+
+    def Compact(self):  # noqa: N802
+        """Not in the reference: one compaction pass on demand -> (the CompactionMetadata of what was compacted or None,
+        err). UnsupportedError without CompactOnDevice(); nothing runs under DisableCompactions()."""
+        from sstables import UnsupportedError
+
+        err = self._check()
+        if err is not None:
+            return None, err
+        if not self.compactOnDevice:
+            return None, UnsupportedError("compactions run under CompactOnDevice() only")
+        return self._compaction_pass()
 
     def Apply(self, batch: "WriteBatch"):  # noqa: N802
         """What a loop of PutBytes / DeleteBytes over the batch leaves: per op the WAL record, the memstore op and,

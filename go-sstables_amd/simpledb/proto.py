@@ -9,6 +9,9 @@ proto.Marshal with deterministic field order and proto3 defaults omitted. unmars
 proto.Unmarshal into a reset WalMutation, the host mirror of the device parser (pb_wal_mutation_t,
 csrc/rio_pb.h) and the one-record path: recovery runs it on the one record the device refused, for the error
 text. Bulk parsing runs on the device (rio_wal_ops_plan).
+
+CompactionMetadata (simpledb/proto/compaction_metadata.proto) is the one record of a compaction's
+compaction_successful file: marshal_compaction_metadata / unmarshal_compaction_metadata, with the same rules.
 """
 from __future__ import annotations
 
@@ -152,6 +155,70 @@ def unmarshal_wal_mutation(b) -> WalMutation:
                     raise InvalidUTF8Error(f"proto.{_MESSAGE[num]}.{name}")
                 setattr(m, name, payload)
                 pos += fl
+    except InvalidUTF8Error:
+        raise
+    except ValueError as e:
+        raise WireError(f"cannot parse invalid wire-format data ({e})") from None
+    return m
+
+
+@dataclass
+class CompactionMetadata:
+    """simpledb/proto/compaction_metadata.proto: message CompactionMetadata { string writePath = 1;
+    string replacementPath = 2; repeated string sstablePaths = 3; }. Paths are str; bytes that are not UTF-8
+    cannot be a field's value (surrogate escapes marshal back to them and fail the check)."""
+
+    writePath: str = ""
+    replacementPath: str = ""
+    sstablePaths: "list[str]" = None
+
+    def __post_init__(self):
+        self.sstablePaths = list(self.sstablePaths or [])
+
+
+_COMPACTION_FIELDS = {1: "writePath", 2: "replacementPath", 3: "sstablePaths"}
+
+
+def marshal_compaction_metadata(m: CompactionMetadata) -> bytes:
+    """proto.Marshal(CompactionMetadata): fields in number order, the empty singular strings left out, every
+    element of the repeated field written (an empty one too). A string that is not valid UTF-8 raises
+    InvalidUTF8Error, as proto.Marshal refuses it."""
+    out = []
+    for num, vals in ((1, [m.writePath]), (2, [m.replacementPath]), (3, m.sstablePaths)):
+        for v in vals:
+            b = v.encode("utf-8", "surrogateescape") if isinstance(v, str) else bytes(v)
+            if not utf8_valid(b):
+                raise InvalidUTF8Error(f"proto.CompactionMetadata.{_COMPACTION_FIELDS[num]}")
+            if b or num == 3:
+                out.append(_field(num, b))
+    return b"".join(out)
+
+
+def unmarshal_compaction_metadata(b) -> CompactionMetadata:
+    """proto.Unmarshal(b, &CompactionMetadata{}): fields in wire order, a singular field keeps its last
+    occurrence, the repeated one appends; a known field with another wire type and unknown fields are skipped;
+    every string must be valid UTF-8. Raises WireError / InvalidUTF8Error (both ValueError)."""
+    m = CompactionMetadata()
+    b = b"" if b is None else bytes(b)
+    pos = 0
+    try:
+        while pos < len(b):
+            num, wt, pos = _tag(b, pos)
+            name = _COMPACTION_FIELDS.get(num)
+            if name is None or wt != 2:
+                pos = _skip(b, pos, len(b), num, wt)
+                continue
+            ln, pos = _varint(b, pos)
+            if ln > len(b) - pos:
+                raise ValueError("truncated field")
+            payload = b[pos:pos + ln]
+            pos += ln
+            if not utf8_valid(payload):
+                raise InvalidUTF8Error(f"proto.CompactionMetadata.{name}")
+            if num == 3:
+                m.sstablePaths.append(payload.decode())
+            else:
+                setattr(m, name, payload.decode())
     except InvalidUTF8Error:
         raise
     except ValueError as e:

@@ -237,6 +237,64 @@ class _DeviceTable:
         self.h_data_flags = self.db.flags[:self.n_data].cpu().tolist()
         self.h_view = u(self.view, 2 * self.n_data) if v0 else None
 
+    @classmethod
+    def from_compaction(cls, base: str, device: int, c, data_bytes: bytes, index_bytes: bytes):
+        """The table a merge has just written under `base`, loaded from what the merge left in HBM
+        (merger.Compaction) instead of from its files: the IndexEntry arena rio_sst_index_encode wrote is the
+        decoded index file (index.rio holds exactly those records, uncompressed), the gathered values are the
+        decoded data file. Only rio_sst_index_parse runs; the stored checksum is the CRC-64 of the value as
+        merged, so `crc` is its copy and nothing is hashed. data_bytes / index_bytes: the file images as written.
+        Fills the fields __init__ fills. Call under torch.cuda.device(device)."""
+        import torch
+
+        from recordio.device import DecodeBuffers, DeviceDecoder, header_codec
+
+        from .merger import check_status, on_device_stream
+
+        self = cls.__new__(cls)
+        self.dec = DeviceDecoder(device)
+        dev = f"cuda:{device}"
+        n = c.n_out
+        self.index_img, self.data_img = index_bytes, data_bytes
+        self.ib = DecodeBuffers(out=c.entries, out_off=c.ent_off, rec_off=c.index_rec_off,
+                                flags=torch.zeros(max(n, 1), dtype=torch.uint8, device=dev), info=None)
+        self.db = DecodeBuffers(out=c.values, out_off=c.val_off, rec_off=c.data_rec_off, flags=c.val_flags, info=None)
+
+        def info(img, total):  # what the decode reports for a whole file of n good records
+            return dict(version=int.from_bytes(img[0:4], "little"), compression=header_codec(img) or L.COMP_NONE,
+                        n_records=n, total_out_bytes=total, status=L.RIO_EOF, status_offset=len(img), detail0=0,
+                        detail1=0, n_chunks=0, n_repairs=0, first_bad=_NONE, n_bad=0)
+
+        self.index_info, self.data_info = info(index_bytes, c.ent_bytes), info(data_bytes, c.value_bytes)
+        self.index_bad = self.value_bad = self.bad_crc = self.unplaced = _NONE
+        self.n_index = self.n_data = n
+        self.v0 = False
+        i64 = lambda: torch.empty(max(n, 1), dtype=torch.int64, device=dev)  # noqa: E731
+        self.key_off, self.key_len, self.value_off, self.checksum = i64(), i64(), i64(), i64()
+        res = torch.empty(2, dtype=torch.int64, device=dev)
+
+        def run(st):
+            check_status(L.lib().rio_sst_index_parse(self.dec.ctx, c.entries.data_ptr(), c.ent_off.data_ptr(), n,
+                                                     self.key_off.data_ptr(), self.key_len.data_ptr(),
+                                                     self.value_off.data_ptr(), self.checksum.data_ptr(), res.data_ptr(), st),
+                         "rio_sst_index_parse")
+
+        on_device_stream(device, run)
+        self.crc = self.checksum.clone()
+        self.bad_proto = int(res[0].item()) & _NONE
+        if self.bad_proto != _NONE:
+            raise GoError(f"sstable '{base}': index entry {self.bad_proto} of the merge does not parse")
+        u = lambda t, k: [x & _NONE for x in t[:k].cpu().tolist()]  # noqa: E731
+        self.h_key_off, self.h_key_len = u(self.key_off, n), u(self.key_len, n)
+        self.h_value_off, self.h_checksum = u(self.value_off, n), u(self.checksum, n)
+        self.h_crc = list(self.h_checksum)
+        self.h_index = bytes(c.entries[:c.ent_bytes].cpu().numpy())
+        self.h_data = bytes(c.values[:c.value_bytes].cpu().numpy())
+        self.h_data_off = u(c.val_off, n + 1)
+        self.h_data_flags = c.val_flags[:n].cpu().tolist()
+        self.h_view = None
+        return self
+
     def key(self, i) -> bytes:
         o = self.h_key_off[i]
         return self.h_index[o:o + self.h_key_len[i]]

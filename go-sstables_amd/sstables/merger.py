@@ -67,6 +67,13 @@ class Compaction:
     first_dup = unsorted_table = _NONE
     out_src = data_img = data_len = index_img = index_len = None
     bloom = None  # (host Filter, DeviceFilter) when the table gets a bloom.bf.gz
+    # the table as it stands decoded in HBM once encode_planned is through: the gathered values (arena, n + 1 offsets,
+    # per-value flags), the IndexEntry records (arena, n + 1 offsets) and each record's offset in its file image.
+    # _DeviceTable.from_compaction loads the table from them
+    values = val_off = val_flags = entries = ent_off = data_rec_off = index_rec_off = None
+    ent_bytes = 0
+    # what write_table_files wrote: the MetaData, the host bloom Filter (None without one), the two file images
+    meta = filter = data_file = index_file = None
 
 
 def on_device_stream(device: int, fn):
@@ -97,7 +104,8 @@ def encode_planned(ctx, device: int, st, src, keep, res, comp: int, mark, refuse
     are the plan's outputs. Shared by compact_on_device and memstore.flush_ops_on_device.
     flt: None, an empty sstables.bloom.Filter (sstables.writer_filter), or a callable n_out -> Filter: its
     bits are built on the device from the survivors' keys (rio_sst_bloom_add: one Add per WriteNext,
-    sstable_writer.go:114-118) and fetched with the file images by write_table_files."""
+    sstable_writer.go:114-118) and fetched with the file images by write_table_files. The gathered values, the
+    IndexEntry records and the records' file offsets stay on the returned Compaction (the written table, decoded)."""
     import torch
 
     lib = L.lib()
@@ -151,6 +159,9 @@ def encode_planned(ctx, device: int, st, src, keep, res, comp: int, mark, refuse
                                  c.index_img.data_ptr(), icap, index_rec_off.data_ptr(), c.index_len.data_ptr(), st),
            "rio_device_encode(index)")
     mark("index_encode")
+    c.values, c.val_off, c.val_flags = values, val_off, val_flags
+    c.entries, c.ent_off, c.ent_bytes = entries, ent_off, ent_bytes
+    c.data_rec_off, c.index_rec_off = data_rec_off, index_rec_off
     return c
 
 
@@ -199,6 +210,8 @@ def write_table_files(path: str, c: Compaction, min_key: bytes, max_key: bytes):
         err = out.WriteFile(os.path.join(path, BloomFileName))
         if err is not None:
             raise err
+        c.filter = out
+    c.meta, c.data_file, c.index_file = meta, data, index
 
 
 def refuse_inputs(readers):
@@ -232,6 +245,7 @@ class SSTableMerger:
     def __init__(self, comp=None, data_compression: int = L.COMP_SNAPPY):
         """comp: bytes comparator only (skiplist.BytesComparator, the reference's default)."""
         self.data_compression = data_compression
+        self.compaction = None  # the last written table's Compaction: its buffers stay in HBM while this holds them
 
     def Merge(self, readers, writer_path: str, data_compression=None, writer_options=()):  # noqa: N802
         """SSTableMerger.Merge (sstable_merger.go:41-68): every entry of every table, nil values too. Two
@@ -285,6 +299,7 @@ class SSTableMerger:
                 lo = readers[first >> L.RIO_MERGE_ENTRY_BITS].t.key(first & _ENTRY_MASK)
                 hi = readers[last >> L.RIO_MERGE_ENTRY_BITS].t.key(last & _ENTRY_MASK)
             write_table_files(path, c, lo, hi)
+            self.compaction = c
         return None
 
 
