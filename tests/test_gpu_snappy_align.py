@@ -2,10 +2,13 @@
 
 The decoder places every piece destination-aligned (bytes [d - r, d - r + 16), r = d & 3) and reads
 its source from q - r: ring copies from the LDS history, literals from the input image, far copies
-(offset > 192) from the arena, and far copies whose source starts in the first bytes of the arena
-from q itself (the lane of a file's first record). These streams hit each source kind at every
+(offset > kFarOff = 232) from the arena, and far copies whose source starts in the first bytes of
+the arena from q itself (the lane of a file's first record). `mixed` draws its long copies from
+offsets above 192, on both sides of that boundary; tests/test_gpu_snappy_lane_stream.py walks the
+boundary offset by offset. These streams hit each source kind at every
 destination alignment, overlapping copies of every short offset, long literals and copies at the
 16-bit length / offset forms, against the oracle's golang/snappy restatement (decode_other.go).
+The element and stream builders are tests/snappy_streams.py's.
 """
 import random
 
@@ -15,58 +18,13 @@ import corpus
 import oracle_py as orc
 from recordio import _lib as L
 from gpu_util import assert_same_as_oracle, gpu_decode_arrays
+from snappy_streams import Stream, file_of
 
 pytestmark = pytest.mark.gpu
 
 
-def lit(b: bytes) -> bytes:
-    n = len(b) - 1
-    if n < 60:
-        return bytes([n << 2]) + b
-    if n < 256:
-        return bytes([60 << 2, n]) + b
-    return bytes([61 << 2, n & 0xFF, n >> 8]) + b
-
-
-def copy(off: int, ln: int) -> bytes:
-    if 4 <= ln <= 11 and off < 2048:
-        return bytes([1 | ((ln - 4) << 2) | ((off >> 8) << 5), off & 0xFF])
-    if off < 65536:
-        return bytes([2 | ((ln - 1) << 2), off & 0xFF, off >> 8])
-    return bytes([3 | ((ln - 1) << 2)]) + off.to_bytes(4, "little")
-
-
-class Stream:
-    """A snappy block built element by element, with the decoded bytes kept to size copies."""
-
-    def __init__(self):
-        self.els = bytearray()
-        self.out = bytearray()
-
-    def literal(self, b: bytes):
-        self.els += lit(b)
-        self.out += b
-
-    def copy(self, off: int, ln: int):
-        assert 1 <= off <= len(self.out) and 1 <= ln <= 64
-        self.els += copy(off, ln)
-        for _ in range(ln):
-            self.out.append(self.out[-off])
-
-    def payload(self) -> bytes:
-        return corpus.uvarint(len(self.out)) + bytes(self.els)
-
-
-def file_of(streams) -> bytes:
-    img = bytearray(corpus.file_header(4, 2))
-    for st in streams:
-        pay = st.payload()
-        img += corpus.header_v4(len(st.out), len(pay)) + pay
-    return bytes(img)
-
-
 def far_from_start(rng) -> Stream:
-    """Far copies (offset > 192) whose source is the record's byte 0, 1 or 2, at every destination
+    """Far copies (offset > kFarOff) whose source is the record's byte 0, 1 or 2, at every destination
     alignment: as record 0 of a file, 16 bytes from q - r would start below the arena."""
     st = Stream()
     st.literal(bytes(rng.randrange(256) for _ in range(250)))
