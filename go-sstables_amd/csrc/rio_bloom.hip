@@ -27,6 +27,7 @@
 #include "rio_device.h"
 #include "rio_dev_util.h"
 #include "rio_launch.h"
+#include "rio_seg_copy.h"
 #include "rio_sst_keys.h"
 
 namespace rio {
@@ -123,30 +124,24 @@ __global__ void __launch_bounds__(256) k_sst_lookup(BloomParams P, LookupParams 
     }
 }
 
-namespace {
-unsigned grid_for(uint64_t n) {
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, kBloomGridCap));
-}
-}  // namespace
-
 hipError_t launch_bloom_add(const BloomParams& P, bool survivors, hipStream_t s) {
-    if (survivors) hipLaunchKernelGGL(k_bloom_add<true>, dim3(grid_for(P.n)), dim3(256), 0, s, P);
-    else hipLaunchKernelGGL(k_bloom_add<false>, dim3(grid_for(P.n)), dim3(256), 0, s, P);
+    if (survivors) hipLaunchKernelGGL(k_bloom_add<true>, dim3(grid_for(P.n, 256, kBloomGridCap)), dim3(256), 0, s, P);
+    else hipLaunchKernelGGL(k_bloom_add<false>, dim3(grid_for(P.n, 256, kBloomGridCap)), dim3(256), 0, s, P);
     return hipGetLastError();
 }
 
 hipError_t launch_bloom_contains(const BloomParams& P, hipStream_t s) {
-    hipLaunchKernelGGL(k_bloom_contains, dim3(grid_for(P.n)), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(k_bloom_contains, dim3(grid_for(P.n, 256, kBloomGridCap)), dim3(256), 0, s, P);
     return hipGetLastError();
 }
 
 hipError_t launch_sst_key_prefixes(const rio_sst_view& v, uint64_t* pfx, hipStream_t s) {
-    hipLaunchKernelGGL(k_sst_key_prefixes, dim3(grid_for(v.n)), dim3(256), 0, s, v, pfx);
+    hipLaunchKernelGGL(k_sst_key_prefixes, dim3(grid_for(v.n, 256, kBloomGridCap)), dim3(256), 0, s, v, pfx);
     return hipGetLastError();
 }
 
 hipError_t launch_sst_lookup(const BloomParams& P, const LookupParams& Q, hipStream_t s) {
-    hipLaunchKernelGGL(k_sst_lookup, dim3(grid_for(P.n)), dim3(256), 0, s, P, Q);
+    hipLaunchKernelGGL(k_sst_lookup, dim3(grid_for(P.n, 256, kBloomGridCap)), dim3(256), 0, s, P, Q);
     return hipGetLastError();
 }
 

@@ -24,27 +24,25 @@
 //   k_merge_rank     one lane per input entry: position, keep flag, the result block's sums
 //   k_gather_select  survivors compacted by an exclusive scan of the keep flags: source word,
 //                    value length, nil flag
-//   k_gather_copy<G> G lanes per value (16 for values under kLongValue bytes, a wave for the others):
-//                    bytes up to the destination's next 16-byte boundary, then aligned 16-byte stores
-//                    fed by unaligned 16-byte loads, then the tail bytes; nothing is read or
-//                    written outside the value
+//   k_gather_copy<G> G lanes per value (16 for values under kLongItem bytes, a wave for the others):
+//                    copy_ranges (rio_seg_copy.h); nothing is read or written outside the value
 //   k_entry_len / k_entry_write   IndexEntry sizes, then (after a scan) their bytes
 // Every table and entry index read from a buffer is clamped before use (view_of / entry_of), every
 // key and value range is clamped to its arena, and every store is checked against its capacity: a
 // wrong input gives a status or wrong bytes, never an out-of-range access.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
-
-#include <algorithm>
-
 #include "rio_device.h"
 #include "rio_dev_util.h"
 #include "rio_launch.h"
+#include "rio_seg_copy.h"
 #include "rio_sst_keys.h"
 
 namespace rio {
 
 namespace {
+
+// the lane-per-entry kernels' grid: longer inputs go round the grid-stride loops again
+constexpr uint64_t kMergeGridCap = 4096;
 
 // table of input entry number g: the last t with base[t] <= g (base in LDS, base[T] = N > g)
 __device__ __forceinline__ uint32_t table_of(const uint64_t* base, uint32_t T, uint64_t g) {
@@ -200,34 +198,16 @@ __global__ void __launch_bounds__(256) k_gather_pad(GatherParams P) {
     }
 }
 
-// G lanes per value. kLong = false: values shorter than kLongValue; true: the others.
+// G lanes per value. kLong = false: values shorter than kLongItem; true: the others.
 template <uint32_t G, bool kLong>
 __global__ void __launch_bounds__(256) k_gather_copy(GatherParams P) {
-    const uint32_t lane = threadIdx.x % G;
-    const uint64_t grp = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
-    const uint64_t ngrp = ((uint64_t)gridDim.x * blockDim.x) / G;
-    for (uint64_t j = grp; j < P.n_out; j += ngrp) {
-        const uint64_t d0 = P.val_off[j], d1 = P.val_off[j + 1];
-        const uint64_t len = d1 - d0;
-        if (len == 0 || (len >= kLongValue) != kLong || d1 > P.values_cap || d1 < d0) continue;
+    copy_ranges<G, kLong>(P.n_out, P.val_off, P.values_cap, P.values, [&](uint64_t j, uint64_t len) __attribute__((always_inline)) -> const uint8_t* {
         const rio_sst_view* v;
         uint64_t i, vb, ve;
-        if (!entry_of(P.views, P.T, P.out_src[j], v, i)) continue;
+        if (!entry_of(P.views, P.T, P.out_src[j], v, i)) return nullptr;
         value_at(*v, i, vb, ve);
-        if (ve - vb != len) continue;  // the lengths scanned are these same ranges
-        const uint8_t* s = v->data + vb;
-        uint8_t* d = P.values + d0;
-        // bytes up to the destination's next 16-byte boundary (the arena base is 16-byte aligned or
-        // not: the address decides), whole aligned 16-byte words, then the tail. The same text as copy_item
-        // (rio_dev_util.h), kept in line here: the call compiles this kernel to other code (two more VGPRs)
-        const uint64_t head = umin((uint64_t)((16 - (reinterpret_cast<uintptr_t>(d) & 15)) & 15), len);
-        if (lane < head) d[lane] = s[lane];
-        const uint64_t body = (len - head) & ~15ull;
-        for (uint64_t k = head + 16ull * lane; k < head + body; k += 16ull * G)
-            *reinterpret_cast<uint4*>(d + k) = ldu16(s + k);
-        const uint64_t t0 = head + body;
-        if (t0 + lane < len && lane < 16) d[t0 + lane] = s[t0 + lane];
-    }
+        return ve - vb == len ? v->data + vb : nullptr;
+    });
 }
 
 __global__ void __launch_bounds__(256) k_entry_len(EntryParams P) {
@@ -245,15 +225,6 @@ __global__ void __launch_bounds__(256) k_entry_len(EntryParams P) {
     }
 }
 
-__device__ __forceinline__ uint8_t* put_varint(uint8_t* p, uint64_t v) {
-    while (v >= 0x80) {
-        *p++ = (uint8_t)(v | 0x80);
-        v >>= 7;
-    }
-    *p++ = (uint8_t)v;
-    return p;
-}
-
 __global__ void __launch_bounds__(256) k_entry_write(EntryParams P) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < P.n_out; j += stride) {
@@ -269,64 +240,47 @@ __global__ void __launch_bounds__(256) k_entry_write(EntryParams P) {
         uint8_t* p = P.entries + e0;
         if (k.len) {
             *p++ = 0x0A;  // field 1, wire type 2
-            p = put_varint(p, k.len);
+            p = pb_put_varint(p, k.len);
             for (uint64_t b = 0; b < k.len; b++) p[b] = k.p[b];
             p += k.len;
         }
         if (vo) {
             *p++ = 0x10;  // field 2, varint
-            p = put_varint(p, vo);
+            p = pb_put_varint(p, vo);
         }
         if (cs) {
             *p++ = 0x18;  // field 3, varint
-            p = put_varint(p, cs);
+            p = pb_put_varint(p, cs);
         }
     }
-}
-
-static unsigned grid_for(uint64_t n, uint64_t per_block) {
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + per_block - 1) / per_block, 4096));
-}
-
-size_t merge_cub_bytes(uint64_t n) {
-    size_t b = 0;
-    if (hipcub::DeviceScan::ExclusiveSum(nullptr, b, (uint64_t*)nullptr, (uint64_t*)nullptr, (int)(n + 1)) != hipSuccess)
-        return 0;
-    return b;
 }
 
 hipError_t launch_merge_plan(const MergeParams& P, hipStream_t s) {
     hipLaunchKernelGGL(k_merge_init, dim3(1), dim3(64), 0, s, P.result);
     if (P.N) {
-        hipLaunchKernelGGL(k_merge_keys, dim3(grid_for(P.N, 256)), dim3(256), 0, s, P);
-        hipLaunchKernelGGL(k_merge_rank, dim3(grid_for(P.N, 256)), dim3(256), 0, s, P);
+        hipLaunchKernelGGL(k_merge_keys, dim3(grid_for(P.N, 256, kMergeGridCap)), dim3(256), 0, s, P);
+        hipLaunchKernelGGL(k_merge_rank, dim3(grid_for(P.N, 256, kMergeGridCap)), dim3(256), 0, s, P);
     }
     return hipGetLastError();
 }
 
 hipError_t launch_merge_gather(const GatherParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s) {
-    hipLaunchKernelGGL(k_gather_flags, dim3(grid_for(P.N + 1, 256)), dim3(256), 0, s, P);
-    size_t tb = cub_bytes;
-    hipError_t e = hipcub::DeviceScan::ExclusiveSum(cub_tmp, tb, P.tmp, P.opos, (int)(P.N + 1), s);
+    hipLaunchKernelGGL(k_gather_flags, dim3(grid_for(P.N + 1, 256, kMergeGridCap)), dim3(256), 0, s, P);
+    hipError_t e = launch_offsets_scan(cub_tmp, cub_bytes, P.tmp, P.opos, P.N, s);
     if (e != hipSuccess) return e;
-    if (P.N) hipLaunchKernelGGL(k_gather_select, dim3(grid_for(P.N, 256)), dim3(256), 0, s, P);
-    hipLaunchKernelGGL(k_gather_pad, dim3(grid_for(P.n_out + 1, 256)), dim3(256), 0, s, P);
-    tb = cub_bytes;
-    e = hipcub::DeviceScan::ExclusiveSum(cub_tmp, tb, P.tmp, P.val_off, (int)(P.n_out + 1), s);
+    if (P.N) hipLaunchKernelGGL(k_gather_select, dim3(grid_for(P.N, 256, kMergeGridCap)), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(k_gather_pad, dim3(grid_for(P.n_out + 1, 256, kMergeGridCap)), dim3(256), 0, s, P);
+    e = launch_offsets_scan(cub_tmp, cub_bytes, P.tmp, P.val_off, P.n_out, s);
     if (e != hipSuccess) return e;
-    if (P.n_out) {
-        hipLaunchKernelGGL((k_gather_copy<16, false>), dim3(grid_for(P.n_out, 16)), dim3(256), 0, s, P);
-        hipLaunchKernelGGL((k_gather_copy<64, true>), dim3(grid_for(P.n_out, 4)), dim3(256), 0, s, P);
-    }
+    if (P.n_out) launch_short_long(k_gather_copy<16, false>, k_gather_copy<64, true>, P.n_out, P, s);
     return hipGetLastError();
 }
 
 hipError_t launch_index_entries(const EntryParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s) {
-    hipLaunchKernelGGL(k_entry_len, dim3(grid_for(P.n_out + 1, 256)), dim3(256), 0, s, P);
-    size_t tb = cub_bytes;
-    hipError_t e = hipcub::DeviceScan::ExclusiveSum(cub_tmp, tb, P.tmp, P.ent_off, (int)(P.n_out + 1), s);
+    hipLaunchKernelGGL(k_entry_len, dim3(grid_for(P.n_out + 1, 256, kMergeGridCap)), dim3(256), 0, s, P);
+    hipError_t e = launch_offsets_scan(cub_tmp, cub_bytes, P.tmp, P.ent_off, P.n_out, s);
     if (e != hipSuccess) return e;
-    if (P.n_out) hipLaunchKernelGGL(k_entry_write, dim3(grid_for(P.n_out, 256)), dim3(256), 0, s, P);
+    if (P.n_out) hipLaunchKernelGGL(k_entry_write, dim3(grid_for(P.n_out, 256, kMergeGridCap)), dim3(256), 0, s, P);
     return hipGetLastError();
 }
 

@@ -6,19 +6,18 @@
 //                       (table_status, rio_sst_keys.h), then db.go's rules in order: the table's read error first
 //                       (:212-218), a memstore's value (:240-241, an empty one too), a memstore's tombstone
 //                       (:231-234), the table's non-empty value (:228-229), else not found; the scan's input
-//   k_db_value_copy<G>  G lanes per value (16 under kLongValue bytes, a wave for the others): copy_item from the op
-//                       log's value arena (RIO_GET_MEM_VALUE) or the table's data arena (RIO_GET_VALUE)
+//   k_db_value_copy<G>  G lanes per value (16 under kLongItem bytes, a wave for the others): copy_ranges
+//                       (rio_seg_copy.h) from the op log's value arena (RIO_GET_MEM_VALUE) or the table's data
+//                       arena (RIO_GET_VALUE)
 // Every store, op, table and entry number read from a buffer is clamped (mem_op_of, entry_of), every range to its
 // arena, every store is checked against values_cap: a wrong input gives RIO_GET_NOT_FOUND or wrong bytes, never an
 // out-of-range access.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
-
-#include <algorithm>
 
 #include "rio_device.h"
 #include "rio_dev_util.h"
 #include "rio_launch.h"
+#include "rio_seg_copy.h"
 #include "rio_ops_keys.h"
 #include "rio_sst_keys.h"
 
@@ -27,7 +26,6 @@ namespace rio {
 namespace {
 // 256 CUs x 8 blocks of 256 lanes: longer batches go round the grid-stride loops again
 constexpr uint64_t kDbGridCap = 2048;
-constexpr uint64_t kDbCopyGridCap = 4096;
 }  // namespace
 
 // status and value length per query; position n holds the scan's last input, 0
@@ -62,63 +60,38 @@ __global__ void __launch_bounds__(256) k_db_value_len(DbParams P) {
     }
 }
 
-// G lanes per value. kLong = false: values shorter than kLongValue; true: the others.
+// G lanes per value. kLong = false: values shorter than kLongItem; true: the others.
 template <uint32_t G, bool kLong>
 __global__ void __launch_bounds__(256) k_db_value_copy(DbParams P) {
-    const uint32_t lane = threadIdx.x % G;
-    const uint64_t grp = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
-    const uint64_t ngrp = ((uint64_t)gridDim.x * blockDim.x) / G;
-    for (uint64_t j = grp; j < P.n; j += ngrp) {
-        const uint64_t d0 = P.val_off[j], d1 = P.val_off[j + 1];
-        if (d1 <= d0 || d1 > P.values_cap) continue;
-        const uint64_t len = d1 - d0;
-        if ((len >= kLongValue) != kLong) continue;
+    copy_ranges<G, kLong>(P.n, P.val_off, P.values_cap, P.values, [&](uint64_t j, uint64_t len) __attribute__((always_inline)) -> const uint8_t* {
         const uint32_t status = P.status[j];
-        const uint8_t* from;
         uint64_t vb, ve;
         if (status == RIO_GET_MEM_VALUE) {
             const rio_mem_index* I;
             uint64_t op;
-            if (!mem_op_of(P.i0, P.i1, P.n_idx, P.mem_src[j], I, op)) continue;
+            if (!mem_op_of(P.i0, P.i1, P.n_idx, P.mem_src[j], I, op)) return nullptr;
             value_range(I->ops, op, vb, ve);
-            from = I->ops.values;
-        } else if (status == RIO_GET_VALUE && P.tab_src) {
+            return ve - vb == len ? I->ops.values + vb : nullptr;
+        }
+        if (status == RIO_GET_VALUE && P.tab_src) {
             const rio_sst_view* v;
             uint64_t i;
-            if (!entry_of(P.views, P.T, P.tab_src[j], v, i)) continue;
+            if (!entry_of(P.views, P.T, P.tab_src[j], v, i)) return nullptr;
             value_at(*v, i, vb, ve);
-            from = v->data;
-        } else {
-            continue;
+            return ve - vb == len ? v->data + vb : nullptr;
         }
-        if (ve - vb != len) continue;  // the lengths scanned are these same ranges
-        copy_item<G>(P.values + d0, from + vb, len, lane);
-    }
-}
-
-namespace {
-unsigned grid_for(uint64_t n, uint64_t per_block, uint64_t cap) {
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + per_block - 1) / per_block, cap));
-}
-}  // namespace
-
-size_t db_cub_bytes(uint64_t n) {
-    size_t b = 0;
-    if (hipcub::DeviceScan::ExclusiveSum(nullptr, b, (uint64_t*)nullptr, (uint64_t*)nullptr, (int)(n + 1)) != hipSuccess)
-        return 0;
-    return b;
+        return nullptr;
+    });
 }
 
 hipError_t launch_db_value_plan(const DbParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s) {
     hipLaunchKernelGGL(k_db_value_len, dim3(grid_for(P.n + 1, 256, kDbGridCap)), dim3(256), 0, s, P);
-    size_t tb = cub_bytes;
-    hipError_t e = hipcub::DeviceScan::ExclusiveSum(cub_tmp, tb, P.tmp, P.val_off, (int)(P.n + 1), s);
+    const hipError_t e = launch_offsets_scan(cub_tmp, cub_bytes, P.tmp, P.val_off, P.n, s);
     return e != hipSuccess ? e : hipGetLastError();
 }
 
 hipError_t launch_db_value_copy(const DbParams& P, hipStream_t s) {
-    hipLaunchKernelGGL((k_db_value_copy<16, false>), dim3(grid_for(P.n, 16, kDbCopyGridCap)), dim3(256), 0, s, P);
-    hipLaunchKernelGGL((k_db_value_copy<64, true>), dim3(grid_for(P.n, 4, kDbCopyGridCap)), dim3(256), 0, s, P);
+    launch_short_long(k_db_value_copy<16, false>, k_db_value_copy<64, true>, P.n, P, s);
     return hipGetLastError();
 }
 

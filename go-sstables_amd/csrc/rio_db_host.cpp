@@ -282,7 +282,7 @@ extern "C" int rio_db_reader_create(rio_ctx* ctx, rio_sst_stack* stack, uint64_t
         r->T = stack->P.T;
     }
     HIP_TRY(r->tmp.ensure(max_batch * 8 + 8));
-    HIP_TRY(r->cub.ensure(std::max<size_t>(db_cub_bytes(max_batch), 256)));
+    HIP_TRY(r->cub.ensure(std::max<size_t>(scan_cub_bytes(max_batch), 256)));
     *out = r.release();
     return RIO_OK;
 }

@@ -68,21 +68,6 @@ __device__ __forceinline__ void stu16_nt(uint8_t* p, uint4 v) {
     v4u32u w = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(w, reinterpret_cast<v4u32u*>(p));
 }
-// len bytes from s to d by G lanes (lane = this lane's number among them): bytes up to the destination's next
-// 16-byte boundary (the address decides), whole aligned 16-byte stores fed by unaligned 16-byte loads, then the
-// tail bytes. Nothing is read outside [s, s + len) or written outside [d, d + len). k_gather_copy's scheme
-// (rio_compact.hip, which keeps its own text of it); the copy body of k_wal_copy (rio_walops.hip) and of the
-// stack's value and key copies (rio_stack.hip)
-template <uint32_t G>
-__device__ __forceinline__ void copy_item(uint8_t* d, const uint8_t* s, uint64_t len, uint32_t lane) {
-    const uint64_t head = umin((uint64_t)((16 - (reinterpret_cast<uintptr_t>(d) & 15)) & 15), len);
-    if (lane < head) d[lane] = s[lane];
-    const uint64_t body = (len - head) & ~15ull;
-    for (uint64_t k = head + 16ull * lane; k < head + body; k += 16ull * G)
-        *reinterpret_cast<uint4*>(d + k) = ldu16(s + k);
-    const uint64_t t0 = head + body;
-    if (t0 + lane < len && lane < 16) d[t0 + lane] = s[t0 + lane];
-}
 
 __device__ __forceinline__ uint4 zero4() { return make_uint4(0, 0, 0, 0); }
 __device__ __forceinline__ uint4 or4(uint4 a, uint4 b) { return make_uint4(a.x | b.x, a.y | b.y, a.z | b.z, a.w | b.w); }

@@ -462,6 +462,15 @@ RIO_HD inline uint32_t pb_varint_len(uint64_t v) {
     }
     return n;
 }
+// v as a varint at p (pb_varint_len(v) bytes); returns the byte behind it
+RIO_HD inline uint8_t* pb_put_varint(uint8_t* p, uint64_t v) {
+    while (v >= 0x80) {
+        *p++ = (uint8_t)(v | 0x80);
+        v >>= 7;
+    }
+    *p++ = (uint8_t)v;
+    return p;
+}
 RIO_HD inline uint64_t pb_index_entry_len(uint64_t key_len, uint64_t value_off, uint64_t checksum) {
     return (key_len ? 1 + pb_varint_len(key_len) + key_len : 0) + (value_off ? 1 + pb_varint_len(value_off) : 0) +
            (checksum ? 1 + pb_varint_len(checksum) : 0);

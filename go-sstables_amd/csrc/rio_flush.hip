@@ -38,6 +38,7 @@
 #include "rio_device.h"
 #include "rio_dev_util.h"
 #include "rio_launch.h"
+#include "rio_seg_copy.h"
 #include "rio_ops_keys.h"
 
 namespace rio {
@@ -162,10 +163,6 @@ __global__ void __launch_bounds__(256) k_flush_crc(FlushParams P) {
 
 namespace {
 
-unsigned grid_for(uint64_t n) {
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, kFlushGridCap));
-}
-
 struct PassBits {
     int begin, end;
 };
@@ -217,7 +214,7 @@ hipError_t launch_flush_plan(const FlushParams& P, hipStream_t s, hipEvent_t* ev
     hipLaunchKernelGGL(k_flush_init, dim3(1), dim3(64), 0, s, P.result);
     *n_stages = 0;
     if (!n) return hipGetLastError();
-    const dim3 g(grid_for(n)), b(256);
+    const dim3 g(grid_for(n, 256, kFlushGridCap)), b(256);
     stamp();
     hipLaunchKernelGGL(k_flush_check, g, b, 0, s, P);
     stamp();

@@ -52,8 +52,11 @@ hipError_t launch_sst_validate(const uint8_t* data, const uint64_t* data_off, co
                                const uint64_t* view = nullptr);
 hipError_t launch_sst_data_entry(const uint8_t* arena, const uint64_t* off, uint64_t n, uint64_t* view,
                                  uint64_t* result, hipStream_t s);
+// rio_scan.hip: the exclusive sum of n + 1 lengths (the last one 0) into n + 1 offsets, and its scratch size
+size_t scan_cub_bytes(uint64_t n);
+hipError_t launch_offsets_scan(void* cub_tmp, size_t cub_bytes, const uint64_t* in, uint64_t* out, uint64_t n,
+                               hipStream_t s);
 // rio_compact.hip
-size_t merge_cub_bytes(uint64_t n);
 hipError_t launch_merge_plan(const MergeParams& P, hipStream_t s);
 hipError_t launch_merge_gather(const GatherParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
 hipError_t launch_index_entries(const EntryParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
@@ -63,7 +66,6 @@ hipError_t launch_bloom_contains(const BloomParams& P, hipStream_t s);
 hipError_t launch_sst_key_prefixes(const rio_sst_view& v, uint64_t* pfx, hipStream_t s);
 hipError_t launch_sst_lookup(const BloomParams& P, const LookupParams& Q, hipStream_t s);
 // rio_stack.hip
-size_t stack_cub_bytes(uint64_t n);
 hipError_t launch_stack_lookup(const StackParams& P, hipStream_t s);
 hipError_t launch_stack_value_plan(const StackParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
 hipError_t launch_stack_value_copy(const StackParams& P, hipStream_t s);
@@ -84,15 +86,12 @@ hipError_t launch_ops_rebase(const OpsRebaseParams& P, hipStream_t s);
 size_t mem_size_cub_bytes(uint64_t n);
 hipError_t launch_mem_size(const MemSizeParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
 // rio_db.hip
-size_t db_cub_bytes(uint64_t n);
 hipError_t launch_db_value_plan(const DbParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
 hipError_t launch_db_value_copy(const DbParams& P, hipStream_t s);
 // rio_walops.hip
-size_t wal_cub_bytes(uint64_t n);
 hipError_t launch_wal_plan(const WalParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
 hipError_t launch_wal_gather(const WalParams& P, hipStream_t s);
 // rio_walenc.hip
-size_t walenc_cub_bytes(uint64_t n);
 hipError_t launch_walenc(const WalEncParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
 // rio_encode.hip
 hipError_t launch_encode(const EncParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);

@@ -47,6 +47,7 @@
 #include "rio_device.h"
 #include "rio_dev_util.h"
 #include "rio_launch.h"
+#include "rio_seg_copy.h"
 #include "rio_ops_keys.h"
 #include "rio_sst_keys.h"
 
@@ -90,12 +91,6 @@ __global__ void __launch_bounds__(256) k_mem_lookup(MemLookupParams P) {
     }
 }
 
-namespace {
-unsigned grid_for(uint64_t n) {
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, kMemGridCap));
-}
-}  // namespace
-
 size_t mem_index_cub_bytes(uint64_t n) {
     size_t b = 0;
     if (hipcub::DeviceSelect::Flagged(nullptr, b, (const uint64_t*)nullptr, (const uint8_t*)nullptr, (uint64_t*)nullptr,
@@ -110,12 +105,12 @@ hipError_t launch_mem_index(const MemBuildParams& P, void* cub_tmp, size_t cub_b
     const hipError_t e = hipcub::DeviceSelect::Flagged(cub_tmp, tb, P.src, P.keep, P.order, P.n_sel, (int)P.ops.n, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_mem_seal, dim3(1), dim3(64), 0, s, P.result);
-    hipLaunchKernelGGL(k_mem_prefix, dim3(grid_for(P.ops.n)), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(k_mem_prefix, dim3(grid_for(P.ops.n, 256, kMemGridCap)), dim3(256), 0, s, P);
     return hipGetLastError();
 }
 
 hipError_t launch_mem_lookup(const MemLookupParams& P, hipStream_t s) {
-    hipLaunchKernelGGL(k_mem_lookup, dim3(grid_for(P.n)), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(k_mem_lookup, dim3(grid_for(P.n, 256, kMemGridCap)), dim3(256), 0, s, P);
     return hipGetLastError();
 }
 
@@ -258,26 +253,22 @@ __global__ void __launch_bounds__(256) k_ops_rebase(OpsRebaseParams P) {
 }
 
 size_t mem_extend_cub_bytes(uint64_t t) {
-    size_t b = 0;
-    if (hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)(t + 1)) != hipSuccess)
-        return 0;
-    return std::max(b, mem_index_cub_bytes(t));
+    return std::max(scan_cub_bytes(t), mem_index_cub_bytes(t));
 }
 
 // after the tail's launch_flush_plan and launch_mem_index (into P.b_order, P.b_pfx, P.b_result) on the same stream
 hipError_t launch_mem_extend(const MemExtendParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s) {
-    hipLaunchKernelGGL(k_mem_rank, dim3(grid_for(P.t + 1)), dim3(256), 0, s, P);
-    size_t tb = cub_bytes;
-    const hipError_t e = hipcub::DeviceScan::ExclusiveSum(cub_tmp, tb, (const uint64_t*)P.eq, P.e, (int)(P.t + 1), s);
+    hipLaunchKernelGGL(k_mem_rank, dim3(grid_for(P.t + 1, 256, kMemGridCap)), dim3(256), 0, s, P);
+    const hipError_t e = launch_offsets_scan(cub_tmp, cub_bytes, P.eq, P.e, P.t, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_mem_place, dim3(grid_for(P.ops.n)), dim3(256), 0, s, P);
-    hipLaunchKernelGGL(k_mem_copy_back, dim3(grid_for(P.ops.n)), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(k_mem_place, dim3(grid_for(P.ops.n, 256, kMemGridCap)), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(k_mem_copy_back, dim3(grid_for(P.ops.n, 256, kMemGridCap)), dim3(256), 0, s, P);
     hipLaunchKernelGGL(k_mem_extend_seal, dim3(1), dim3(64), 0, s, P);
     return hipGetLastError();
 }
 
 hipError_t launch_ops_rebase(const OpsRebaseParams& P, hipStream_t s) {
-    hipLaunchKernelGGL(k_ops_rebase, dim3(grid_for(P.n)), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(k_ops_rebase, dim3(grid_for(P.n, 256, kMemGridCap)), dim3(256), 0, s, P);
     return hipGetLastError();
 }
 

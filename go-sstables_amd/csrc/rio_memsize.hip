@@ -34,6 +34,7 @@
 #include "rio_device.h"
 #include "rio_dev_util.h"
 #include "rio_launch.h"
+#include "rio_seg_copy.h"
 #include "rio_ops_keys.h"
 #include "rio_sst_keys.h"
 
@@ -131,12 +132,6 @@ __global__ void k_size_seal(MemSizeParams P) {
     R[RIO_SIZE_R_FIRST_BAD] = bad;
 }
 
-namespace {
-unsigned grid_for(uint64_t n) {
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, kSizeGridCap));
-}
-}  // namespace
-
 size_t mem_size_cub_bytes(uint64_t n) {
     size_t b = 0;
     if (hipcub::DeviceScan::InclusiveSum(nullptr, b, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)n) != hipSuccess)
@@ -148,11 +143,11 @@ size_t mem_size_cub_bytes(uint64_t n) {
 hipError_t launch_mem_size(const MemSizeParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s) {
     const uint64_t n = P.batch.n;
     if (n) {
-        hipLaunchKernelGGL(k_size_delta, dim3(grid_for(n)), dim3(256), 0, s, P);
+        hipLaunchKernelGGL(k_size_delta, dim3(grid_for(n, 256, kSizeGridCap)), dim3(256), 0, s, P);
         size_t tb = cub_bytes;
         const hipError_t e = hipcub::DeviceScan::InclusiveSum(cub_tmp, tb, (const uint64_t*)P.delta, P.size, (int)n, s);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_size_cut, dim3(grid_for(n)), dim3(256), 0, s, P);
+        hipLaunchKernelGGL(k_size_cut, dim3(grid_for(n, 256, kSizeGridCap)), dim3(256), 0, s, P);
     }
     hipLaunchKernelGGL(k_size_seal, dim3(1), dim3(64), 0, s, P);
     return hipGetLastError();

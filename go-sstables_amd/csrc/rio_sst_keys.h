@@ -13,8 +13,6 @@ namespace rio {
 
 constexpr uint64_t kEntryMask = (1ull << RIO_MERGE_ENTRY_BITS) - 1;
 
-constexpr uint64_t kLongValue = 1024;  // values from this length on are copied by a whole wave
-
 // value i of a view: [b, e) clamped to the data arena
 __device__ __forceinline__ bool value_at(const rio_sst_view& v, uint64_t i, uint64_t& b, uint64_t& e) {
     const uint64_t o0 = v.data_off[i], o1 = v.data_off[i + 1];

@@ -17,20 +17,19 @@
 //                       found predicate and a block-wide skip) was measured beside it and not kept: DESIGN.md
 //                       §4; its text is in profiles/r10/README.md
 //   k_stack_value_len   one lane per query: status byte (RIO_GET_*) and value length, the scan's input
-//   k_stack_value_copy<G>  G lanes per value (16 under kLongValue bytes, a wave for the others): copy_item
+//   k_stack_value_copy<G>  G lanes per value (16 under kLongItem bytes, a wave for the others): copy_ranges
+//                       (rio_seg_copy.h)
 //   k_stack_bounds      one lane per (key, table): lower or upper bound
-//   k_keys_len / k_keys_copy<G>  key lengths of a plan's survivors, then (after a scan) their bytes: copy_item
+//   k_keys_len / k_keys_copy<G>  key lengths of a plan's survivors, then (after a scan) their bytes: copy_ranges
 // Every table and entry number read from a buffer is clamped (entry_of), every key and value range is clamped
 // to its arena, every store is checked against its capacity: a wrong input gives ~0, RIO_GET_NOT_FOUND or wrong
 // bytes, never an out-of-range access.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
-
-#include <algorithm>
 
 #include "rio_device.h"
 #include "rio_dev_util.h"
 #include "rio_launch.h"
+#include "rio_seg_copy.h"
 #include "rio_sst_keys.h"
 
 namespace rio {
@@ -39,7 +38,6 @@ namespace {
 
 // 256 CUs x 8 blocks of 256 lanes: longer batches go round the grid-stride loops again
 constexpr uint64_t kStackGridCap = 2048;
-constexpr uint64_t kStackCopyGridCap = 4096;
 
 // query i of the arena: clamped to [0, key_bytes); room = bytes readable from its first byte
 __device__ __forceinline__ Key query_key(const StackParams& P, uint64_t i, uint64_t& room) {
@@ -94,24 +92,16 @@ __global__ void __launch_bounds__(256) k_stack_value_len(StackParams P) {
     }
 }
 
-// G lanes per value. kLong = false: values shorter than kLongValue; true: the others.
+// G lanes per value. kLong = false: values shorter than kLongItem; true: the others.
 template <uint32_t G, bool kLong>
 __global__ void __launch_bounds__(256) k_stack_value_copy(StackParams P) {
-    const uint32_t lane = threadIdx.x % G;
-    const uint64_t grp = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
-    const uint64_t ngrp = ((uint64_t)gridDim.x * blockDim.x) / G;
-    for (uint64_t j = grp; j < P.n; j += ngrp) {
-        const uint64_t d0 = P.val_off[j], d1 = P.val_off[j + 1];
-        if (d1 <= d0 || d1 > P.values_cap) continue;
-        const uint64_t len = d1 - d0;
-        if ((len >= kLongValue) != kLong) continue;
+    copy_ranges<G, kLong>(P.n, P.val_off, P.values_cap, P.values, [&](uint64_t j, uint64_t len) __attribute__((always_inline)) -> const uint8_t* {
         const rio_sst_view* v;
         uint64_t i, vb, ve;
-        if (!entry_of(P.views, P.T, P.src[j], v, i)) continue;
+        if (!entry_of(P.views, P.T, P.src[j], v, i)) return nullptr;
         value_at(*v, i, vb, ve);
-        if (ve - vb != len) continue;  // the lengths scanned are these same ranges
-        copy_item<G>(P.values + d0, v->data + vb, len, lane);
-    }
+        return ve - vb == len ? v->data + vb : nullptr;
+    });
 }
 
 __global__ void __launch_bounds__(256) k_stack_bounds(StackParams P) {
@@ -143,35 +133,14 @@ __global__ void __launch_bounds__(256) k_keys_len(KeysParams P) {
 
 template <uint32_t G, bool kLong>
 __global__ void __launch_bounds__(256) k_keys_copy(KeysParams P) {
-    const uint32_t lane = threadIdx.x % G;
-    const uint64_t grp = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
-    const uint64_t ngrp = ((uint64_t)gridDim.x * blockDim.x) / G;
-    for (uint64_t j = grp; j < P.n_out; j += ngrp) {
-        const uint64_t d0 = P.key_off[j], d1 = P.key_off[j + 1];
-        if (d1 <= d0 || d1 > P.keys_cap) continue;
-        const uint64_t len = d1 - d0;
-        if ((len >= kLongValue) != kLong) continue;
+    copy_ranges<G, kLong>(P.n_out, P.key_off, P.keys_cap, P.keys, [&](uint64_t j, uint64_t len) __attribute__((always_inline)) -> const uint8_t* {
         const rio_sst_view* v;
         uint64_t i;
-        if (!entry_of(P.views, P.T, P.out_src[j], v, i)) continue;
+        if (!entry_of(P.views, P.T, P.out_src[j], v, i)) return nullptr;
         bool ok;
         const Key k = key_at(*v, i, ok);
-        if (k.len != len) continue;
-        copy_item<G>(P.keys + d0, k.p, len, lane);
-    }
-}
-
-namespace {
-unsigned grid_for(uint64_t n, uint64_t per_block, uint64_t cap) {
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + per_block - 1) / per_block, cap));
-}
-}  // namespace
-
-size_t stack_cub_bytes(uint64_t n) {
-    size_t b = 0;
-    if (hipcub::DeviceScan::ExclusiveSum(nullptr, b, (uint64_t*)nullptr, (uint64_t*)nullptr, (int)(n + 1)) != hipSuccess)
-        return 0;
-    return b;
+        return k.len == len ? k.p : nullptr;
+    });
 }
 
 hipError_t launch_stack_lookup(const StackParams& P, hipStream_t s) {
@@ -181,14 +150,12 @@ hipError_t launch_stack_lookup(const StackParams& P, hipStream_t s) {
 
 hipError_t launch_stack_value_plan(const StackParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s) {
     hipLaunchKernelGGL(k_stack_value_len, dim3(grid_for(P.n + 1, 256, kStackGridCap)), dim3(256), 0, s, P);
-    size_t tb = cub_bytes;
-    hipError_t e = hipcub::DeviceScan::ExclusiveSum(cub_tmp, tb, P.tmp, P.val_off, (int)(P.n + 1), s);
+    const hipError_t e = launch_offsets_scan(cub_tmp, cub_bytes, P.tmp, P.val_off, P.n, s);
     return e != hipSuccess ? e : hipGetLastError();
 }
 
 hipError_t launch_stack_value_copy(const StackParams& P, hipStream_t s) {
-    hipLaunchKernelGGL((k_stack_value_copy<16, false>), dim3(grid_for(P.n, 16, kStackCopyGridCap)), dim3(256), 0, s, P);
-    hipLaunchKernelGGL((k_stack_value_copy<64, true>), dim3(grid_for(P.n, 4, kStackCopyGridCap)), dim3(256), 0, s, P);
+    launch_short_long(k_stack_value_copy<16, false>, k_stack_value_copy<64, true>, P.n, P, s);
     return hipGetLastError();
 }
 
@@ -199,13 +166,9 @@ hipError_t launch_stack_bounds(const StackParams& P, hipStream_t s) {
 
 hipError_t launch_keys_gather(const KeysParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s) {
     hipLaunchKernelGGL(k_keys_len, dim3(grid_for(P.n_out + 1, 256, kStackGridCap)), dim3(256), 0, s, P);
-    size_t tb = cub_bytes;
-    hipError_t e = hipcub::DeviceScan::ExclusiveSum(cub_tmp, tb, P.tmp, P.key_off, (int)(P.n_out + 1), s);
+    const hipError_t e = launch_offsets_scan(cub_tmp, cub_bytes, P.tmp, P.key_off, P.n_out, s);
     if (e != hipSuccess) return e;
-    if (P.n_out) {
-        hipLaunchKernelGGL((k_keys_copy<16, false>), dim3(grid_for(P.n_out, 16, kStackCopyGridCap)), dim3(256), 0, s, P);
-        hipLaunchKernelGGL((k_keys_copy<64, true>), dim3(grid_for(P.n_out, 4, kStackCopyGridCap)), dim3(256), 0, s, P);
-    }
+    if (P.n_out) launch_short_long(k_keys_copy<16, false>, k_keys_copy<64, true>, P.n_out, P, s);
     return hipGetLastError();
 }
 

@@ -67,7 +67,7 @@ extern "C" int rio_sst_stack_create(rio_ctx* ctx, const rio_sst_view* views, con
     st->max_batch = max_batch;
     HIP_TRY(st->tables.ensure(host.size() * 8));
     HIP_TRY(st->tmp.ensure(max_batch * 8 + 8));
-    HIP_TRY(st->cub.ensure(std::max<size_t>(stack_cub_bytes(max_batch), 256)));
+    HIP_TRY(st->cub.ensure(std::max<size_t>(scan_cub_bytes(max_batch), 256)));
     hipStream_t s = rio::stream_of(ctx, stream);
     HIP_TRY(hipMemcpyAsync(st->tables.p, host.data(), host.size() * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));  // `host` is read by that copy; the only wait of the stack's life

@@ -97,7 +97,7 @@ extern "C" int rio_sst_merge_plan(rio_ctx* ctx, const rio_sst_view* views, uint3
     HIP_TRY(M.pfx.ensure(N * 8 + 8));
     HIP_TRY(M.tmp.ensure(N * 8 + 8));
     HIP_TRY(M.opos.ensure(N * 8 + 8));
-    HIP_TRY(M.cub.ensure(std::max<size_t>(merge_cub_bytes(N), 256)));
+    HIP_TRY(M.cub.ensure(std::max<size_t>(scan_cub_bytes(N), 256)));
     hipStream_t s = stream_of(ctx, stream);
     HIP_TRY(M.views.upload(host, s));
     MergeParams P{};
@@ -284,7 +284,7 @@ int rio::flush_plan(rio_ctx* ctx, const rio_ops_view* ops, uint32_t mode, uint32
     HIP_TRY(M.views.dev.ensure(host.size() * 8));
     HIP_TRY(M.tmp.ensure(n * 8 + 8));
     HIP_TRY(M.opos.ensure(n * 8 + 8));
-    HIP_TRY(M.cub.ensure(std::max<size_t>(merge_cub_bytes(n), 256)));
+    HIP_TRY(M.cub.ensure(std::max<size_t>(scan_cub_bytes(n), 256)));
     HIP_TRY(F.len.ensure(n * 8 + 8));
     HIP_TRY(F.crc.ensure(n * 8 + 8));
     HIP_TRY(F.dig.ensure(2 * n * 8 + 16));
@@ -381,7 +381,7 @@ extern "C" int rio_wal_ops_plan(rio_ctx* ctx, const rio_wal_segment* segs, uint3
     const size_t words = 8 * (N + 1) + 2;
     HIP_TRY(W.segs.dev.ensure(host.size() * 8));
     HIP_TRY(W.scr.ensure(words * 8 + 4 * (N + 1)));
-    HIP_TRY(W.cub.ensure(std::max<size_t>(wal_cub_bytes(N), 256)));
+    HIP_TRY(W.cub.ensure(std::max<size_t>(scan_cub_bytes(N), 256)));
     hipStream_t s = stream_of(ctx, stream);
     HIP_TRY(W.segs.upload(host, s));
     WalParams P{};
@@ -444,7 +444,7 @@ extern "C" int rio_wal_ops_encode(rio_ctx* ctx, const rio_ops_view* ops, uint8_t
     HIP_TRY(hipSetDevice(ctx->device));
     rio_ctx::WalEnc& W = ctx->walenc;
     HIP_TRY(W.scr.ensure((n + 1 + 4) * 8));
-    HIP_TRY(W.cub.ensure(std::max<size_t>(walenc_cub_bytes(n), 256)));
+    HIP_TRY(W.cub.ensure(std::max<size_t>(scan_cub_bytes(n), 256)));
     WalEncParams P{};
     P.ops = *ops;
     P.records = d_records;

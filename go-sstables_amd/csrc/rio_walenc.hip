@@ -15,22 +15,20 @@
 //                    round and word)
 //   1 exclusive scan (hipcub::DeviceScan) over n + 1 items into the caller's rec_off; item n is the arena length
 //   k_walenc_result  the result block
-//   k_walenc_write<G, kLong>  G lanes per record (16 for items under kWalEncLongItem bytes, a wave for the others; a
+//   k_walenc_write<G, kLong>  G lanes per record (16 for items under kLongItem bytes, a wave for the others; a
 //                    record's key and value each go to the instantiation of their length). The instantiation of the
 //                    key's length writes the record's header bytes (at most 33, in two pieces: before the key and
 //                    before the value) from one lane with plain byte stores; the group copies with copy_item
-//                    (rio_dev_util.h). Two records in flight per group, as k_wal_copy.
+//                    (rio_seg_copy.h). Two records in flight per group, as k_wal_copy.
 // Every offset read back from a buffer is clamped to its arena again in the write kernel, a record is written only
 // when its scanned range equals the length computed from the clamped ranges and ends inside records_cap: a wrong
 // input gives RIO_WAL_BAD_RANGE or unwritten records, never an out-of-range access.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
-
-#include <algorithm>
 
 #include "rio_device.h"
 #include "rio_dev_util.h"
 #include "rio_launch.h"
+#include "rio_seg_copy.h"
 
 namespace rio {
 
@@ -38,33 +36,17 @@ namespace {
 
 // 256 CUs x 4 blocks of 256 lanes: longer logs go round the grid-stride loop again
 constexpr uint64_t kWalEncGridCap = 1024;
-// the write kernels' grid (a block of 256 lanes takes 2 x 16 or 2 x 4 records per round)
+// the shared copy grid and threshold (rio_seg_copy.h) under this file's own names: a reader of this
+// file alone (a test that sizes its cases by them) finds the figures here, and the build fails if they part
 constexpr uint64_t kWalEncCopyGridCap = 4096;
-constexpr uint64_t kWalEncLongItem = 1024;  // items from this length on are copied by a whole wave
+constexpr uint64_t kWalEncLongItem = 1024;
+static_assert(kWalEncCopyGridCap == kCopyGridCap && kWalEncLongItem == kLongItem, "the shared copy constants");
 
 constexpr uint32_t kMetaBad = 0, kMetaMaxKey = 1, kMetaUpserts = 2, kMetaDeletes = 3;
 
-__device__ __forceinline__ uint32_t varint_len(uint64_t v) {
-    uint32_t n = 1;
-    while (v >= 0x80) {
-        v >>= 7;
-        n++;
-    }
-    return n;
-}
-
-__device__ __forceinline__ uint8_t* put_varint(uint8_t* p, uint64_t v) {
-    while (v >= 0x80) {
-        *p++ = (uint8_t)(v | 0x80);
-        v >>= 7;
-    }
-    *p++ = (uint8_t)v;
-    return p;
-}
-
 // a length-delimited field: tag, length, payload; nothing for an empty payload (proto3)
 __device__ __forceinline__ uint64_t field_len(uint64_t payload) {
-    return payload ? 1 + varint_len(payload) + payload : 0;
+    return payload ? 1 + pb_varint_len(payload) + payload : 0;
 }
 
 // op g of the log: its clamped key and value ranges and what its record looks like
@@ -85,7 +67,7 @@ __device__ __forceinline__ EncOp enc_op(const rio_ops_view& v, uint64_t g) {
     o.ko = kb, o.kl = ke - kb;
     o.vo = vb, o.vl = o.del ? 0 : ve - vb;
     o.body = field_len(o.kl) + field_len(o.vl);
-    o.len = 1 + varint_len(o.body) + o.body;
+    o.len = 1 + pb_varint_len(o.body) + o.body;
     return o;
 }
 
@@ -150,16 +132,9 @@ __global__ void k_walenc_result(WalEncParams P) {
 
 namespace {
 
-// one thing to copy: len = 0 for nothing
-struct EncItem {
-    const uint8_t* s;
-    uint8_t* d;
-    uint64_t len;
-};
-
 // what this instantiation does for record g: its items, and the header when it is the header's writer
 struct EncRec {
-    EncItem k, v;
+    CopyItem k, v;
     uint8_t* d;  // the record's first byte when this instantiation writes the header, else null
     uint64_t body, kl, vl;
     bool del;
@@ -175,15 +150,15 @@ __device__ __forceinline__ void enc_rec(const WalEncParams& P, uint64_t g, EncRe
     R.k.len = R.v.len = 0;
     R.d = nullptr;
     if (o.bad || r1 < r0 || r1 - r0 != o.len || r1 > P.records_cap) return;
-    const uint64_t h1 = 1 + varint_len(o.body) + (o.kl ? 1 + varint_len(o.kl) : 0);  // up to the key's first byte
-    const uint64_t h2 = o.vl ? 1 + varint_len(o.vl) : 0;                              // between key and value
+    const uint64_t h1 = 1 + pb_varint_len(o.body) + (o.kl ? 1 + pb_varint_len(o.kl) : 0);  // up to the key's first byte
+    const uint64_t h2 = o.vl ? 1 + pb_varint_len(o.vl) : 0;                              // between key and value
     uint8_t* d = P.records + r0;
-    if ((o.kl >= kWalEncLongItem) == kLong) {  // the key's instantiation writes the header (an empty key: the short one)
+    if ((o.kl >= kLongItem) == kLong) {  // the key's instantiation writes the header (an empty key: the short one)
         R.d = d;
         R.body = o.body, R.kl = o.kl, R.vl = o.vl, R.del = o.del;
-        if (o.kl) R.k = EncItem{P.ops.keys + o.ko, d + h1, o.kl};
+        if (o.kl) R.k = CopyItem{P.ops.keys + o.ko, d + h1, o.kl};
     }
-    if (o.vl && (o.vl >= kWalEncLongItem) == kLong) R.v = EncItem{P.ops.values + o.vo, d + h1 + o.kl + h2, o.vl};
+    if (o.vl && (o.vl >= kLongItem) == kLong) R.v = CopyItem{P.ops.values + o.vo, d + h1 + o.kl + h2, o.vl};
 }
 
 // the record's header bytes, by one lane: member tag and body length, the key's tag and length, and behind the
@@ -191,14 +166,14 @@ __device__ __forceinline__ void enc_rec(const WalEncParams& P, uint64_t g, EncRe
 __device__ __forceinline__ void enc_header(const EncRec& R) {
     uint8_t* p = R.d;
     *p++ = R.del ? 0x12 : 0x0A;
-    p = put_varint(p, R.body);
+    p = pb_put_varint(p, R.body);
     if (R.kl) {
         *p++ = R.del ? 0x12 : 0x1A;
-        p = put_varint(p, R.kl) + R.kl;
+        p = pb_put_varint(p, R.kl) + R.kl;
     }
     if (R.vl) {
         *p++ = 0x22;
-        put_varint(p, R.vl);
+        pb_put_varint(p, R.vl);
     }
 }
 
@@ -229,34 +204,14 @@ __global__ void __launch_bounds__(256) k_walenc_write(WalEncParams P) {
     }
 }
 
-namespace {
-
-unsigned grid_for(uint64_t n, uint64_t per_block, uint64_t cap) {
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + per_block - 1) / per_block, cap));
-}
-
-}  // namespace
-
-size_t walenc_cub_bytes(uint64_t n) {
-    size_t b = 0;
-    if (hipcub::DeviceScan::ExclusiveSum(nullptr, b, (uint64_t*)nullptr, (uint64_t*)nullptr, (int)(n + 1)) != hipSuccess)
-        return 0;
-    return b;
-}
-
 hipError_t launch_walenc(const WalEncParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s) {
     const uint64_t n = P.ops.n;
     hipLaunchKernelGGL(k_walenc_init, dim3(1), dim3(64), 0, s, P);
     hipLaunchKernelGGL(k_walenc_len, dim3(grid_for(n + 1, 256, kWalEncGridCap)), dim3(256), 0, s, P);
-    size_t tb = cub_bytes;
-    const hipError_t e = hipcub::DeviceScan::ExclusiveSum(cub_tmp, tb, P.len, P.rec_off, (int)(n + 1), s);
+    const hipError_t e = launch_offsets_scan(cub_tmp, cub_bytes, P.len, P.rec_off, n, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_walenc_result, dim3(1), dim3(64), 0, s, P);
-    if (n && P.records_cap) {
-        const dim3 g16(grid_for(n, 16, kWalEncCopyGridCap)), g64(grid_for(n, 4, kWalEncCopyGridCap)), b(256);
-        hipLaunchKernelGGL((k_walenc_write<16, false>), g16, b, 0, s, P);
-        hipLaunchKernelGGL((k_walenc_write<64, true>), g64, b, 0, s, P);
-    }
+    if (n && P.records_cap) launch_short_long(k_walenc_write<16, false>, k_walenc_write<64, true>, n, P, s);
     return hipGetLastError();
 }
 

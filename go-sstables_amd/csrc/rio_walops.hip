@@ -16,18 +16,15 @@
 //   k_wal_result   the result block
 // Gather (rio_wal_ops_gather):
 //   k_wal_offsets  one lane per record: key_off / val_off / flags / op_rec of its op, the final offsets
-//   k_wal_copy<G, kLong>  G lanes per record (16 for items under kWalLongItem bytes, a wave for the others;
-//                  a record's key and value each go to the instantiation of their length), k_gather_copy's
-//                  scheme (rio_compact.hip): bytes up to the destination's next 16-byte boundary, aligned
-//                  16-byte stores fed by unaligned 16-byte loads, the tail bytes; nothing is read or written
-//                  outside the item. A group loads all of a record's bookkeeping words at once and has two
-//                  records in flight. The value copy is the bandwidth path: every value byte is read once
-//                  and written once.
+//   k_wal_copy<G, kLong>  G lanes per record (16 for items under kLongItem bytes, a wave for the others;
+//                  a record's key and value each go to the instantiation of their length), copied with
+//                  copy_item (rio_seg_copy.h); nothing is read or written outside the item. A group loads
+//                  all of a record's bookkeeping words at once and has two records in flight. The value
+//                  copy is the bandwidth path: every value byte is read once and written once.
 // Every record, segment and op number read back from a buffer is clamped, every source range is clamped to
 // its segment's arena again in the gather, and every store is checked against its capacity: a wrong input
 // gives RIO_WAL_BAD_RANGE or wrong bytes, never an out-of-range access.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 
@@ -35,6 +32,7 @@
 #include "rio_dev_util.h"
 #include "rio_launch.h"
 #include "rio_pb.h"
+#include "rio_seg_copy.h"
 
 namespace rio {
 
@@ -44,9 +42,11 @@ static_assert(kPbWalBadProto == RIO_WAL_BAD_PROTO && kPbWalBadUtf8 == RIO_WAL_BA
 
 // 256 CUs x 4 blocks of 256 lanes: longer logs go round the grid-stride loops again
 constexpr uint64_t kWalGridCap = 1024;
-// the copy kernels' grid (a block of 256 lanes takes 2 x 16 or 2 x 4 records per round)
+// the shared copy grid and threshold (rio_seg_copy.h) under this file's own names: a reader of this
+// file alone (a test that sizes its cases by them) finds the figures here, and the build fails if they part
 constexpr uint64_t kWalCopyGridCap = 4096;
-constexpr uint64_t kWalLongItem = 1024;  // items from this length on are copied by a whole wave
+constexpr uint64_t kWalLongItem = 1024;
+static_assert(kWalCopyGridCap == kCopyGridCap && kWalLongItem == kLongItem, "the shared copy constants");
 
 // segment of record g: the last s with base[s] <= g (base[S] = N > g; empty segments repeat a base, the
 // last of equal bases is the one that holds the record)
@@ -181,19 +181,12 @@ __global__ void __launch_bounds__(256) k_wal_offsets(WalParams P) {
     }
 }
 
-// one thing to copy: len = 0 for nothing
-struct WalItem {
-    const uint8_t* s;
-    uint8_t* d;
-    uint64_t len;
-};
-
-// record g's key and value as this instantiation's items (kLong = false: items shorter than kWalLongItem; true:
+// record g's key and value as this instantiation's items (kLong = false: items shorter than kLongItem; true:
 // the others). Every word of the record is loaded before the first is looked at, so the loads are in flight
 // together; the segment and op numbers are clamped, the source ranges clamped to the segment's arena again (the
 // scanned lengths are the ranges the plan checked), the destinations checked against their caps.
 template <bool kLong>
-__device__ __forceinline__ void wal_items(const WalParams& P, uint64_t g, WalItem& k, WalItem& v) {
+__device__ __forceinline__ void wal_items(const WalParams& P, uint64_t g, CopyItem& k, CopyItem& v) {
     const uint32_t rec = P.rec[g];
     const uint64_t kd0 = P.kdst[g], kd1 = P.kdst[g + 1], vd0 = P.vdst[g], vd1 = P.vdst[g + 1];
     const uint64_t j = P.opos[g], ko = P.koff[g], vo = P.voff[g];
@@ -203,18 +196,15 @@ __device__ __forceinline__ void wal_items(const WalParams& P, uint64_t g, WalIte
     const rio_wal_segment& seg = P.segs[sg];
     const uint64_t ob = seg.out_bytes;
     const uint64_t kl = kd1 - kd0, vl = vd1 - vd0;
-    if (kd1 > kd0 && (kl >= kWalLongItem) == kLong && kd1 <= P.keys_cap && ko <= ob && kl <= ob - ko)
-        k = WalItem{seg.out + ko, P.keys + kd0, kl};
-    if (kind == kWalUpsert && vd1 > vd0 && (vl >= kWalLongItem) == kLong && vd1 <= P.values_cap && vo <= ob && vl <= ob - vo)
-        v = WalItem{seg.out + vo, P.values + vd0, vl};
+    if (kd1 > kd0 && (kl >= kLongItem) == kLong && kd1 <= P.keys_cap && ko <= ob && kl <= ob - ko)
+        k = CopyItem{seg.out + ko, P.keys + kd0, kl};
+    if (kind == kWalUpsert && vd1 > vd0 && (vl >= kLongItem) == kLong && vd1 <= P.values_cap && vo <= ob && vl <= ob - vo)
+        v = CopyItem{seg.out + vo, P.values + vd0, vl};
 }
 
-// k_gather_copy's scheme (rio_compact.hip) for one item by G lanes: bytes up to the destination's next 16-byte
-// boundary (the address decides), whole aligned 16-byte words fed by unaligned loads, then the tail
 template <uint32_t G>
-__device__ __forceinline__ void wal_copy_item(const WalItem& it, uint32_t lane) {
-    if (!it.len) return;
-    copy_item<G>(it.d, it.s, it.len, lane);
+__device__ __forceinline__ void wal_copy_item(const CopyItem& it, uint32_t lane) {
+    if (it.len) copy_item<G>(it.d, it.s, it.len, lane);
 }
 
 // G lanes per record, two records per round so that one's bookkeeping loads overlap the other's copy
@@ -224,7 +214,7 @@ __global__ void __launch_bounds__(256) k_wal_copy(WalParams P) {
     const uint64_t grp = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
     const uint64_t ngrp = ((uint64_t)gridDim.x * blockDim.x) / G;
     for (uint64_t g = grp; g < P.N; g += 2 * ngrp) {
-        WalItem k0, v0, k1, v1;
+        CopyItem k0, v0, k1, v1;
         wal_items<kLong>(P, g, k0, v0);
         k1.len = v1.len = 0;
         if (g + ngrp < P.N) wal_items<kLong>(P, g + ngrp, k1, v1);
@@ -235,29 +225,13 @@ __global__ void __launch_bounds__(256) k_wal_copy(WalParams P) {
     }
 }
 
-namespace {
-
-unsigned grid_for(uint64_t n, uint64_t per_block, uint64_t cap) {
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + per_block - 1) / per_block, cap));
-}
-
-}  // namespace
-
-size_t wal_cub_bytes(uint64_t n) {
-    size_t b = 0;
-    if (hipcub::DeviceScan::ExclusiveSum(nullptr, b, (uint64_t*)nullptr, (uint64_t*)nullptr, (int)(n + 1)) != hipSuccess)
-        return 0;
-    return b;
-}
-
 hipError_t launch_wal_plan(const WalParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s) {
     hipLaunchKernelGGL(k_wal_init, dim3(1), dim3(64), 0, s, P);
     hipLaunchKernelGGL(k_wal_parse, dim3(grid_for(P.N + 1, 256, kWalGridCap)), dim3(256), 0, s, P);
     const uint64_t* in[3] = {P.isop, P.klen, P.vlen};
     uint64_t* out[3] = {P.opos, P.kdst, P.vdst};
     for (int k = 0; k < 3; k++) {
-        size_t tb = cub_bytes;
-        const hipError_t e = hipcub::DeviceScan::ExclusiveSum(cub_tmp, tb, in[k], out[k], (int)(P.N + 1), s);
+        const hipError_t e = launch_offsets_scan(cub_tmp, cub_bytes, in[k], out[k], P.N, s);
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(k_wal_result, dim3(1), dim3(64), 0, s, P);
@@ -266,11 +240,7 @@ hipError_t launch_wal_plan(const WalParams& P, void* cub_tmp, size_t cub_bytes, 
 
 hipError_t launch_wal_gather(const WalParams& P, hipStream_t s) {
     hipLaunchKernelGGL(k_wal_offsets, dim3(grid_for(std::max(P.N, P.n_ops) + 1, 256, kWalGridCap)), dim3(256), 0, s, P);
-    if (P.N && P.n_ops) {
-        const dim3 g16(grid_for(P.N, 16, kWalCopyGridCap)), g64(grid_for(P.N, 4, kWalCopyGridCap)), b(256);
-        hipLaunchKernelGGL((k_wal_copy<16, false>), g16, b, 0, s, P);
-        hipLaunchKernelGGL((k_wal_copy<64, true>), g64, b, 0, s, P);
-    }
+    if (P.N && P.n_ops) launch_short_long(k_wal_copy<16, false>, k_wal_copy<64, true>, P.N, P, s);
     return hipGetLastError();
 }
 

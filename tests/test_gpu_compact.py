@@ -173,7 +173,7 @@ def test_merge_keeps_nil_values(tmp_path):
 
 # ---- value lengths and alignment --------------------------------------------------------------------
 
-_LENS = (0, 1, 15, 16, 17, 63, 64, 65, 255, 4096, 70000)
+_LENS = (0, 1, 15, 16, 17, 63, 64, 65, 255, 1023, 1024, 1025, 4096, 70000)
 
 
 @pytest.mark.parametrize("in_comp,out_comp", [(0, 0), (0, 2), (2, 0), (2, 2)])

@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 
 _NONE = 0xFFFFFFFFFFFFFFFF
 BITS = L.RIO_MERGE_ENTRY_BITS
-K_LONG = 1024  # kLongValue (rio_sst_keys.h): values from this length on are copied by a whole wave
+K_LONG = 1024  # kLongItem (rio_seg_copy.h): values and keys from this length on are copied by a whole wave
 P8 = b"prefix_8"
 
 
@@ -438,6 +438,23 @@ def test_scans_equal_the_model(tmp_path):
         it, err = one.ScanRange(be(3), P8 + b"d")
         assert err is None and drain(it) == sm.Stack([tables[t]]).scan(be(3), P8 + b"d")
         one._free_stack()
+    sr._free_stack()
+
+
+def test_scanned_keys_at_the_copy_class_boundary(tmp_path):
+    """k_keys_copy's two instantiations meet at K_LONG, and a key ends its 16-byte words at 15, 16 and 17 bytes."""
+    lens = (15, 16, 17, K_LONG - 1, K_LONG, K_LONG + 1)
+    tables = [{bytes([0x41 + j]) * n: b"old%d" % n for j, n in enumerate(lens)} | {b"B" * K_LONG: None},
+              {bytes([0x61 + j]) * n: val(n % 40, n) for j, n in enumerate(lens)} | {b"B" * 16: b"newer"}]
+    sr = open_stack(tmp_path, tables)
+    model = sm.Stack(tables)
+    every = model.scan()
+    assert sorted(len(k) for k, _ in every) == sorted(lens + lens) and (b"B" * 16, b"newer") in every  # the nil key drops
+    scan, err = sr.ScanOnDevice()
+    assert err is None and device_items(scan) == every
+    for lo, hi in ((b"C" * (K_LONG - 1), b"b" * 16), (b"E" * K_LONG, b"E" * K_LONG), (b"a", b"f" * (K_LONG + 1))):
+        scan, err = sr.ScanRangeOnDevice(lo, hi)
+        assert err is None and device_items(scan) == model.scan(lo, hi) and model.scan(lo, hi), (lo, hi)
     sr._free_stack()
 
 
