@@ -77,12 +77,12 @@ constexpr uint64_t kLaneWalkSmallMin = 512, kLaneWalkSmallChunks = 32768;
 // walk 0.61 -> 0.585, +1.2 %, profiles/r5/r5bl_c4_chunk_ab.txt); not when RIO_CHUNK_BYTES sets the size
 constexpr uint64_t kBigRecordChunk = 65536;
 // Small files walk smaller chunks: the smallest multiple of 4 KiB (the walk's fill round) whose chunk count fits one round
-// of resident walk waves (CUs x 4 SIMDs x RIO_WALK_OCC = 5 waves: 5 120 on MI355X), at least kSmallFileChunkMin; files
+// of resident walk waves (CUs x 4 SIMDs x kWalkOcc, k_walk's launch bound in rio_device.h: 5 120 on MI355X), at least kSmallFileChunkMin; files
 // that need more than one round at the default size keep it. A 32 MiB file's 1 024 default chunks were one wave per SIMD,
 // each walking 32 KiB as a chain of dependent fill rounds; a chunk count just past one round runs a second round for a
 // few waves (round 6 on MI355X: 32 MiB of 1 KiB records 0.117 -> 0.084 ms at 8 KiB chunks; 100 MB 0.171 -> 0.15 ms at
 // 20 KiB (5 059 waves), against 16 KiB (6 100: two rounds) and 19 KiB (5 325); profiles/r6/r6j_small_file_chunks.txt)
-constexpr uint64_t kSmallFileChunkMin = 8192, kWalkWavesPerSimd = 5;
+constexpr uint64_t kSmallFileChunkMin = 8192;
 static uint64_t wave_chunk_bytes(const rio_ctx* ctx, uint64_t len) {
     const uint64_t cb = ctx->fr.chunk_bytes;
     if (!ctx->fr.chunk_auto) return cb;
@@ -205,7 +205,7 @@ extern "C" int rio_ctx_create(int device, rio_ctx** out) {
     F.lane_walk_min = env_u64("RIO_LANE_WALK_MIN", kLaneWalkSmallMin);
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
-        F.walk_slots = (uint64_t)cus * 4 * kWalkWavesPerSimd;
+        F.walk_slots = (uint64_t)cus * 4 * kWalkOcc;
     if (F.lane_chunk_bytes < 64 || F.lane_chunk_bytes > kMaxChunkBytes || (F.lane_chunk_bytes & 15))
         F.lane_chunk_bytes = 16384;
     if (hipHostMalloc(reinterpret_cast<void**>(&F.walk_hint), sizeof(uint64_t), hipHostMallocPortable) != hipSuccess) {

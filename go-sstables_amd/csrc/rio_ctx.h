@@ -145,7 +145,7 @@ struct rio_ctx {
         uint32_t walk_mode = 2;
         uint64_t lane_chunk_bytes = 16384;
         uint64_t lane_walk_min = 512;  // kLaneWalkSmallMin (RIO_LANE_WALK_MIN)
-        uint64_t walk_slots = 5120;    // resident k_walk waves: CUs x 4 SIMDs x kWalkWavesPerSimd (wave_chunk_bytes)
+        uint64_t walk_slots = 5120;    // resident k_walk waves: CUs x 4 SIMDs x kWalkOcc (wave_chunk_bytes)
         uint64_t* walk_hint = nullptr;
         uint64_t coop_min = ~0ull >> 8;
         rio::FileArenas fa;                                   // the single-file calls

@@ -1,6 +1,6 @@
 // rio_decode.cpp — the decode entry points of librio (include/rio.h): the device-resident calls (one file, a batch
 // of files, one record) and the host two-phase API (rio_frame, rio_decode) the cgo binding and the reader handles use.
-// Every decode runs on the device (rio_kernels.hip); host code only moves bytes. There is no CPU decode fallback:
+// Every decode runs on the device (rio_place.hip launches the pipeline); host code only moves bytes. There is no CPU decode fallback:
 // a missing GPU is an error.
 #include <algorithm>
 

@@ -1,4 +1,4 @@
-// rio_device.h — structures shared by the HIP kernels (rio_kernels.hip) and the host runtime
+// rio_device.h — structures shared by the HIP kernels (the .hip files) and the host runtime
 // (rio_ctx.h and the files that include it). Internal to librio; the public boundary is include/rio.h.
 #pragma once
 #include <stdint.h>
@@ -39,6 +39,14 @@ constexpr uint64_t kSinkBytes = (uint64_t)kSnappyBlock / 64 * kSnappyGridMax * 6
 
 // Framing chunks are at most kMaxChunkBytes long (rio_ctx_create caps RIO_CHUNK_BYTES / RIO_LANE_CHUNK_BYTES there)
 constexpr uint64_t kMaxChunkBytes = 1ull << 30;
+
+// minimum waves per SIMD for k_walk (its launch bound; the context sizes small files' chunks by it, rio_ctx.cpp).
+// Round 1: 6 waves with 60 B spilled to scratch beat 5 (walk 0.210 -> 0.185 ms on C2). With the packed DPP fill
+// scans and the 32-bit LEB128 packing the spills landed in the fill loop: 6 waves 0.413 ms on C3, 5 waves (96
+// VGPRs, no scratch) 0.300 ms, against 0.363 before (C2 0.183 -> 0.164 ms); without a bound the compiler takes 4 waves
+constexpr uint32_t kWalkOcc = 5;
+// chunks per block of k_scan_blocks' first level (k_place finds a chunk's block by it)
+constexpr int kScanBlock = 256;
 
 // One walked record: 16 bytes, written by the walks with one store and read by k_place with one load.
 //   len: decoded length (bits 0..60) | kEofBit | kBadBit | kNilBit. k_gz_resize / k_lzw_resize rewrite the length.

@@ -49,10 +49,6 @@ constexpr uint32_t kGzSmallWin = 2048;    // records with decoded size <= this: 
 constexpr uint32_t kGzLargeWin = 32768;   // DEFLATE window (maximum distance)
 constexpr uint32_t kFastBits = 9;         // decode-table bits
 constexpr uint32_t kFastSize = 1u << kFastBits;
-// 1: literal runs decoded several symbols per fast-table read (below, in gz_record)
-#ifndef RIO_GZ_RUN
-#define RIO_GZ_RUN 1
-#endif
 constexpr uint64_t kPayFail = 1ull << 63;    // rec_pay marker: no CRC check by k_gzip_crc (inflate failed,
                                               // or several members, whose CRCs the inflate checked)
 constexpr uint64_t kPayResize = 1ull << 62;  // rec_pay marker: output larger than the framing's size
@@ -459,7 +455,6 @@ __device__ int gz_record(GzLds<kWin, kIn, kDB>& S, const uint8_t* src, uint32_t 
             uint8_t* L = T.lens;
             while (i < total) {
                 B.refill(lane);
-#if RIO_GZ_RUN
               int x;
               if constexpr (G == 64) {
                 // runs of plain code lengths (symbols 0..15) as in the data loop: every offset looked
@@ -497,9 +492,6 @@ __device__ int gz_record(GzLds<kWin, kIn, kDB>& S, const uint8_t* src, uint32_t 
               } else {
                 x = gz_sym(B, T.lfast, T.lcnt, T.lsym);
               }
-#else
-                const int x = gz_sym(B, T.lfast, T.lcnt, T.lsym);
-#endif
                 if (x < 0 || B.overrun()) return kGzCorrupt;
                 uint32_t rep = 1, val = (uint32_t)x;
                 if (x == 16) {
@@ -539,12 +531,8 @@ __device__ int gz_record(GzLds<kWin, kIn, kDB>& S, const uint8_t* src, uint32_t 
             if (!gz_build<G, kDB>(L + 288, ndist, T.dcnt, T.dsym, T.dfast, lane)) return kGzCorrupt;
         }
         // ---- compressed data (huffmanBlock) ----
-#ifdef RIO_GZ_EXP
-        if (RIO_GZ_EXP == 1) return kGzOkChecked;  // timing only: headers and tables, no data
-#endif
         for (;;) {
             B.refill(lane);
-#if RIO_GZ_RUN
             int s;
             if constexpr (G == 64) {
             // Literal runs, several symbols per table read: lane l looks up the code starting l bits
@@ -589,9 +577,6 @@ __device__ int gz_record(GzLds<kWin, kIn, kDB>& S, const uint8_t* src, uint32_t 
             } else {
                 s = gz_sym(B, T.lfast, T.lcnt, T.lsym);
             }
-#else
-            const int s = gz_sym(B, T.lfast, T.lcnt, T.lsym);
-#endif
             if (s < 0 || B.overrun()) return kGzCorrupt;
             if (s < 256) {
                 if (d >= cap) return kCount ? kGzUnsupported : kGzResize;

@@ -1,5 +1,5 @@
 // rio_index.cpp — DiskKeyIndex lookups of librio (include/rio.h): the device-resident batch search and the
-// host-memory rio_index handle (k_index_search / k_index_search_view in rio_kernels.hip, rio_sort.hip).
+// host-memory rio_index handle (k_index_search / k_index_search_view in rio_seek.hip, rio_sort.hip).
 #include <algorithm>
 
 #include "rio_ctx.h"

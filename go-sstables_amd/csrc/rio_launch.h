@@ -2,22 +2,62 @@
 // that defines each function and by every caller, so the compiler checks the two sides against each other.
 // Internal to librio.
 #pragma once
+#ifdef __HIPCC__
+#include <hip/hip_ext.h>  // launch_ev, for the .hip files
+#endif
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "rio_device.h"
 
 namespace rio {
 
-// rio_kernels.hip: framing, placement and the decoders' driver
+// blocks for n items at per_block items a block: at least one, at most cap (the loops are grid-stride)
+inline unsigned grid_for(uint64_t n, uint64_t per_block, uint64_t cap) {
+    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + per_block - 1) / per_block, cap));
+}
+// the same without a cap, for kernels that take one item per lane or group and do not loop
+inline unsigned blocks_for(uint64_t n, unsigned bs) {
+    uint64_t b = (n + bs - 1) / bs;
+    return (unsigned)(b == 0 ? 1 : b);
+}
+
+// Stage timing rides on the kernels' own dispatches (hipExtLaunchKernelGGL's start / stop events): a separate
+// hipEventRecord puts a marker packet between two kernels and cost ~5.6 us of idle queue each (rocprofv3 trace of a
+// C2 step, profiles/r5/r5bh_ext_events_ab.txt); without events the launches are plain. For the .hip files (the host runtime launches no kernel).
+#ifdef __HIPCC__
+template <typename K, typename A>
+inline void launch_ev(K kernel, dim3 g, dim3 b, hipStream_t s, hipEvent_t start, hipEvent_t stop, const A& P) {
+    if (!start && !stop) {
+        hipLaunchKernelGGL(kernel, g, b, 0, s, P);
+        return;
+    }
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) {
+        hipExtLaunchKernelGGL(kernel, g, b, 0, s, start, stop, 0, P);
+        return;
+    }
+    // under stream capture the events become record nodes around the kernel
+    if (start) (void)hipEventRecord(start, s);
+    hipLaunchKernelGGL(kernel, g, b, 0, s, P);
+    if (stop) (void)hipEventRecord(stop, s);
+}
+#endif
+
+// rio_walk.hip: the chunk walk, wave or lane by P.walk_lane (start / stop: the stage events, either may be null)
+void launch_walk(const FrameParams& P, hipStream_t s, hipEvent_t start, hipEvent_t stop);
+// rio_chunk_scan.hip: the chunk-summary scan, also run by the gzip and lzw redo rounds (stop: may be null)
+void launch_chunk_scan(const FrameParams& P, hipStream_t s, hipEvent_t stop);
+// rio_place.hip: the decode pipeline's launch sequence (framing, placement and the decoders' driver)
 hipError_t launch_phase_a(const FrameParams& P, hipStream_t s, hipEvent_t* ev);
 hipError_t launch_frame(const FrameParams& P, hipStream_t s, hipEvent_t* ev);
 hipError_t launch_frame_ev(const FrameParams& P, hipStream_t s, hipEvent_t walk_start, hipEvent_t walk_stop,
                            hipEvent_t scan_stop);
 hipError_t launch_phase_b(const FrameParams& P, hipStream_t s, hipEvent_t* ev, hipEvent_t done = nullptr);
 hipError_t launch_phase_b_batch(const FrameBatch& B, hipStream_t s, hipEvent_t* ev, hipEvent_t done = nullptr);
-// rio_kernels.hip: single-record decode, the SeekNext map, DiskKeyIndex lookups
+// rio_seek.hip: single-record decode, the SeekNext map, DiskKeyIndex lookups
 hipError_t launch_read_at(const uint8_t* f, uint64_t len, uint64_t off, uint8_t* out, uint64_t out_cap,
                           ReadAtResult* res, hipStream_t s);
 hipError_t launch_seek_next(const uint8_t* f, uint64_t len, uint64_t off, uint64_t seek_len, uint8_t* out,
@@ -31,7 +71,7 @@ hipError_t launch_index_search_view(const uint8_t* out, const uint64_t* out_off,
                                     const uint64_t* P, uint64_t K, const uint64_t* R, uint64_t len, const uint8_t* keys,
                                     const uint64_t* key_off, uint64_t nq, const uint32_t* perm, rio_index_hit* hits,
                                     hipStream_t s);
-// rio_snappy.hip, rio_gzip.hip, rio_lzw.hip: the codecs (called by rio_kernels.hip)
+// rio_snappy.hip, rio_gzip.hip, rio_lzw.hip: the codecs (called by rio_place.hip)
 hipError_t launch_snappy_decode(const FrameParams& P, hipStream_t s, bool main);
 hipError_t launch_snappy_batch(const FrameBatch& B, hipStream_t s);
 hipError_t launch_gzip_decode(const FrameParams& P, hipStream_t s);

@@ -26,7 +26,7 @@
 // Sizes: the framing sized each record by its header's u (the reference's buffer size, equal to the
 // decoded length for every file its writer produces). A record whose output differs is not stored: it
 // is marked for k_lzw_resize, which counts it, and the scan, placement and this decoder run again with
-// the counted sizes (the gzip redo round of rio_kernels.hip).
+// the counted sizes (the gzip redo round of rio_place.hip).
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -34,6 +34,7 @@
 #include "rio_device.h"
 #include "rio_dev_util.h"
 #include "rio_launch.h"
+#include "rio_wave.h"
 
 namespace rio {
 
@@ -69,19 +70,7 @@ __device__ __forceinline__ uint64_t lz_bits(uint32_t k) {
     return 9 * a + 10 * b + 11 * c + 12 * d;
 }
 
-// wave-wide inclusive scans on DPP (row shifts within 16-lane rows, then row broadcasts 15 / 31):
-// VALU latency instead of the LDS round trips of __shfl_up (as the Snappy wave decoder's)
-template <bool kMax>
-__device__ __forceinline__ uint32_t wave_incl(uint32_t v) {
-    auto op = [](uint32_t a, uint32_t b) { return kMax ? (a > b ? a : b) : a + b; };
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false));  // row_shr:1
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false));  // row_shr:2
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false));  // row_shr:4
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false));  // row_shr:8
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false));  // row_bcast:15
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false));  // row_bcast:31
-    return v;
-}
+// the wave scans of rio_wave.h in the shape of the call sites below
 __device__ __forceinline__ uint32_t wave_incl_add(uint32_t v, uint32_t) { return wave_incl<false>(v); }
 __device__ __forceinline__ uint32_t wave_incl_max(uint32_t v, uint32_t) { return wave_incl<true>(v); }
 

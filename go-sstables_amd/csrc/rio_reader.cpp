@@ -1,7 +1,7 @@
 // rio_reader.cpp — the reader handles of librio (include/rio.h), which mirror recordio.ReaderI / recordio.ReadAtI:
 //   FileReader  Open/ReadNext/SkipNext/Close   recordio/file_reader.go:26-172, 272-279
 //   MMapReader  Open/ReadNextAt/SeekNext/Size  recordio/mmap_reader.go:25-203, 358-371
-// Every decode runs on the device (rio_kernels.hip); host code only moves bytes, parses the
+// Every decode runs on the device (rio_place.hip, rio_seek.hip); host code only moves bytes, parses the
 // 8-byte file header at Open (readFileHeaderFromBuffer, common_reader.go:22-44) and iterates the
 // decoded arena.
 #include <fcntl.h>
@@ -48,7 +48,7 @@ static int read_at_impl(rio_ctx* ctx, const uint8_t* d_file, uint64_t len, uint6
 // reader handles
 // ------------------------------------------------------------------------------------------
 // MMapReader's view of a decoded file: the FileReader sequence of records (rio_frame + rio_decode,
-// once per reader) and the SeekNext map (build_seek_map, rio_kernels.hip: every 0x91 position P[k]
+// once per reader) and the SeekNext map (build_seek_map, rio_seek.hip: every 0x91 position P[k]
 // and the record R[k] a SeekNext walk reaching it ends at). ReadNextAt at a record start and SeekNext
 // whose walk ends at a decoded record are answered from here by binary search on the calling thread:
 // no kernel, no lock, no copy (the data pointer stays valid until rio_reader_free).

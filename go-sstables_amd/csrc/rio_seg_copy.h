@@ -1,15 +1,14 @@
 // rio_seg_copy.h — segmented copies: n items whose destination ranges are the exclusive scan of their lengths
 // (off[j], off[j + 1]), copied by G lanes per item in two launches: 16 lanes per item under kLongItem bytes, a
-// wave for the others. The copy of one item, the loop with its guards, the grid sizes and the launch pair, once
+// wave for the others. The copy of one item, the loop with its guards, the grid cap and the launch pair (grid_for: rio_launch.h), once
 // for every kernel that copies this way (rio_compact, rio_stack, rio_db, rio_walops, rio_walenc). Included by
 // .hip files only. Internal to librio.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
-
 #include "rio_dev_util.h"
+#include "rio_launch.h"
 
 namespace rio {
 
@@ -53,11 +52,6 @@ __device__ __forceinline__ void copy_ranges(uint64_t n, const uint64_t* off, uin
         const uint8_t* s = src(j, len);
         if (s) copy_item<G>(dst + d0, s, len, lane);
     }
-}
-
-// blocks for n items at per_block items a block: at least one, at most cap (the loops are grid-stride)
-inline unsigned grid_for(uint64_t n, uint64_t per_block, uint64_t cap) {
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + per_block - 1) / per_block, cap));
 }
 
 // a block of 256 lanes takes 16 short or 4 long items per round

@@ -28,12 +28,13 @@
 // Wave-per-record decoder (coop_*, k_snappy_coop_batch): files or arenas past 32-bit positions and
 // streams >= 4 GiB; 64-bit addressing, one 64-byte output window per round with lane = byte.
 // Files whose every record is a single literal (k_place sets ScanState::any_mixed otherwise) are
-// copied by k_copy_records (rio_kernels.hip) and the kernels here exit at once.
+// copied by k_copy_records (rio_place.hip) and the kernels here exit at once.
 #include <hip/hip_runtime.h>
 
 #include "rio_device.h"
 #include "rio_dev_util.h"
 #include "rio_launch.h"
+#include "rio_wave.h"
 
 namespace rio {
 
@@ -204,31 +205,6 @@ __device__ __forceinline__ void coop_bytes8(const uint32_t* in, uint32_t u, uint
     hi = __builtin_amdgcn_alignbyte(d2, d1, r);
 }
 
-// wave-wide inclusive scans on DPP (row shifts within 16-lane rows, then row broadcasts 15 / 31):
-// VALU latency instead of the LDS round trips of __shfl_up
-template <bool kMax>
-__device__ __forceinline__ uint32_t wave_incl(uint32_t v) {
-    auto op = [](uint32_t a, uint32_t b) { return kMax ? (a > b ? a : b) : a + b; };
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false));  // row_shr:1
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false));  // row_shr:2
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false));  // row_shr:4
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false));  // row_shr:8
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false));  // row_bcast:15
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false));  // row_bcast:31
-    return v;
-}
-
-__device__ __forceinline__ uint64_t wave_excl_u64(uint64_t v, uint32_t lane, uint64_t& total) {
-    uint64_t x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t y = __shfl_up(x, d, 64);
-        x += lane >= (uint32_t)d ? y : 0ull;
-    }
-    total = __shfl(x, 63, 64);
-    return x - v;
-}
-
 // the 288 window bytes from aligned address a: one dword per lane + 8 (clamped inside the padded file)
 struct WinRegs {
     uint32_t w0, w1;
@@ -310,7 +286,7 @@ __device__ bool coop_record(const FrameParams& P, CoopLds& S, uint32_t lane, uin
             excl = inc - (uint32_t)olen;
             total = (uint32_t)__shfl(inc, 63, 64);
         } else {
-            excl = wave_excl_u64(olen, lane, total);
+            excl = wave_excl(olen, lane, total);
         }
         const uint64_t de = d + excl;
         bad = bad || (valid && (de + olen > dlen || (!lit && (off == 0 || off > de))));
