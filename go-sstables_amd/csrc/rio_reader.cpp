@@ -573,6 +573,19 @@ extern "C" int rio_reader_seek_next(rio_reader* r, uint64_t offset, uint64_t* re
     }
 }
 
+extern "C" int rio_reader_index_info(rio_reader* r, struct rio_reader_index_info* info) {
+    if (!r || !info) return RIO_ERR_ARG;
+    *info = {};
+    if (!r->open || r->closed || !r->mmap_mode) return RIO_ERR_STATE;
+    const ReadAtIndex* x = readat_index(r);
+    if (x->n == 0) return RIO_OK;  // not built: whatever a failed build left in P / R is not shown
+    info->n_records = x->n;
+    info->n_positions = x->P.size();
+    info->positions = x->P.data();
+    info->ends = x->R.data();
+    return RIO_OK;
+}
+
 extern "C" int rio_reader_set_seek_len(rio_reader* r, uint64_t seek_len) {
     if (!r || seek_len == 0) return RIO_ERR_ARG;
     r->seek_len.store(seek_len, std::memory_order_relaxed);

@@ -193,8 +193,8 @@ __global__ void k_seek_next(const uint8_t* f, uint64_t len, uint64_t off, uint64
 //   k_seek_step: each position's own step (terminal, or the index of the next 0x91 visited);
 //   k_seek_jump: pointer jumping to each walk's end (log2 of the longest walk rounds).
 // ------------------------------------------------------------------------------------------
-constexpr uint64_t kSeekOther = ~0ull >> 1;
-constexpr uint64_t kSeekEof = kSeekOther - 1;  // the walk passed the last 0x91 without a trial ending it: io.EOF
+constexpr uint64_t kSeekOther = RIO_SEEK_END_OTHER;  // rio.h: rio_reader_index_info shows R as it is
+constexpr uint64_t kSeekEof = RIO_SEEK_END_EOF;  // the walk passed the last 0x91 without a trial ending it: io.EOF
 constexpr uint64_t kSeekTerm = 1ull << 63;
 constexpr uint32_t kSegBytes = 4096;
 

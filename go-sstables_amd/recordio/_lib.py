@@ -200,6 +200,21 @@ class IndexHit(ctypes.Structure):
     ]
 
 
+RIO_SEEK_END_OTHER = (1 << 63) - 1
+RIO_SEEK_END_EOF = RIO_SEEK_END_OTHER - 1
+
+
+class ReaderIndexInfo(ctypes.Structure):
+    """struct rio_reader_index_info (include/rio.h)."""
+
+    _fields_ = [
+        ("n_records", c_uint64),
+        ("n_positions", c_uint64),
+        ("positions", POINTER(c_uint64)),
+        ("ends", POINTER(c_uint64)),
+    ]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "rio_strerror": (c_char_p, [c_int]),
@@ -253,6 +268,7 @@ _SIGS = {
     "rio_reader_seek_next": (
         c_int, [c_void_p, c_uint64, POINTER(c_uint64), POINTER(c_void_p), POINTER(c_uint64), POINTER(c_int)]),
     "rio_reader_set_seek_len": (c_int, [c_void_p, c_uint64]),
+    "rio_reader_index_info": (c_int, [c_void_p, POINTER(ReaderIndexInfo)]),
     "rio_reader_file_info": (c_int, [c_void_p, POINTER(FileInfo)]),
     "rio_writer_new": (c_int, [c_char_p, c_uint32, POINTER(c_void_p)]),
     "rio_writer_write": (c_int, [c_void_p, c_void_p, c_uint64, POINTER(c_uint64)]),

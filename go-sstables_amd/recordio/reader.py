@@ -232,6 +232,20 @@ class MMapReader(_Reader):
             return ro.value, None, None
         return ro.value, (ctypes.string_at(data.value, n.value) if n.value else b""), None
 
+    def index_info(self):
+        """rio_reader_index_info: (n_records, positions, ends) of the reader's decoded index and SeekNext
+        map as numpy copies (n_records 0: not built, the arrays empty), or None on a status."""
+        import numpy as np
+
+        info = L.ReaderIndexInfo()
+        if L.lib().rio_reader_index_info(self._h, byref(info)) != L.RIO_OK:
+            return None
+        k = int(info.n_positions)
+        if k == 0:
+            return int(info.n_records), np.zeros(0, np.uint64), np.zeros(0, np.uint64)
+        return (int(info.n_records), np.ctypeslib.as_array(info.positions, shape=(k,)).copy(),
+                np.ctypeslib.as_array(info.ends, shape=(k,)).copy())
+
     @property
     def seekLen(self):  # noqa: N802
         return self._seek_len if hasattr(self, "_seek_len") else 4096

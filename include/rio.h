@@ -996,6 +996,23 @@ int rio_reader_seek_next(rio_reader* r, uint64_t offset, uint64_t* rec_offset, c
                          uint64_t* len, int* is_nil);
 /* MMapReader.seekLen (mmap_reader.go:370, default 4096; tests shrink it to 10) */
 int rio_reader_set_seek_len(rio_reader* r, uint64_t seek_len);
+/* A read-only view of what the ReadAtI calls above answer from (open MMAP-mode readers; RIO_ERR_STATE
+ * otherwise, RIO_ERR_ARG on a null argument): the decoded record count and the SeekNext map, every
+ * 0x91 offset of the file with the end of a SeekNext walk from it. Builds the index if no call has
+ * yet; nothing else does. n_records == 0 means the index was not built (a framing / decode error, a
+ * refused header, a failed allocation, a decoded size over RIO_READAT_INDEX_MAX): the single-record
+ * kernels answer every call and the two arrays are empty. The pointers are into the reader's index,
+ * valid until rio_reader_free. (A struct tag, not a typedef: C keeps typedef and function names in
+ * one namespace, and the call carries the same name.) */
+#define RIO_SEEK_END_OTHER (~0ull >> 1)             /* the walk ends at a trial outside the decoded sequence */
+#define RIO_SEEK_END_EOF   (RIO_SEEK_END_OTHER - 1) /* the walk runs to the file end: io.EOF */
+struct rio_reader_index_info {
+    uint64_t n_records;        /* decoded records the index serves; 0 = not built, the kernels answer everything */
+    uint64_t n_positions;      /* K */
+    const uint64_t* positions; /* P[K]: every 0x91 offset, ascending */
+    const uint64_t* ends;      /* R[K]: record number < n_records, RIO_SEEK_END_EOF or RIO_SEEK_END_OTHER */
+};
+int rio_reader_index_info(rio_reader* r, struct rio_reader_index_info* info);
 /* whole-file result of a file reader after its (lazy) device decode (RIO_ERR_STATE when windowed) */
 int rio_reader_file_info(rio_reader* r, rio_file_info* info);
 /* File readers decode files larger than 256 MiB in 128 MiB windows (rio_stream_*); before the first
