@@ -166,6 +166,11 @@ struct rio_ctx {
         rio_file_info frame_info{};
     } host;
 
+    // rio_device_read_at_plan (rio_decode.cpp): the scan input (n + 1 words) and the scan temp; grow-only
+    struct ReadAtBatch {
+        rio::DevBuf tmp, cub;
+    } rab;
+
     // rio_sst_open (rio_tables.cpp): parsed index fields (4 x n), per-entry CRC-64, kernel results, v0 value ranges
     struct Sst {
         rio::DevBuf fields, crc, res, view;

@@ -1,5 +1,5 @@
 // rio_decode.cpp — the decode entry points of librio (include/rio.h): the device-resident calls (one file, a batch
-// of files, one record) and the host two-phase API (rio_frame, rio_decode) the cgo binding and the reader handles use.
+// of files, one record, a batch of records) and the host two-phase API (rio_frame, rio_decode) the cgo binding and the reader handles use.
 // Every decode runs on the device (rio_place.hip launches the pipeline); host code only moves bytes. There is no CPU decode fallback:
 // a missing GPU is an error.
 #include <algorithm>
@@ -133,6 +133,58 @@ extern "C" int rio_device_read_at(rio_ctx* ctx, const uint8_t* d_file, uint64_t 
     if (detail0) *detail0 = r.det0;
     if (detail1) *detail1 = r.det1;
     return r.status;
+}
+
+// a batch of ReadNextAt queries on a device-resident file: the plan / copy pair (k_readat_locate, k_readat_copy:
+// rio_seek.hip; k_readat_snappy: rio_snappy.hip). Stream-ordered. No host synchronisation but one: the context's scan
+// arenas only grow, and a DevBuf that grows frees its old allocation with hipFree, which waits for the device. The arenas
+// are the context's, so one context serves one stream at a time for these calls (rio.h)
+static int read_at_batch_args(const rio_ctx* ctx, const uint8_t* d_file, uint64_t n, const void* a, const void* b,
+                              const void* c) {
+    if (!ctx || !d_file || (reinterpret_cast<uintptr_t>(d_file) & 15) != 0) return RIO_ERR_ARG;
+    if (n && (!a || !b || !c)) return RIO_ERR_ARG;
+    if (n >= (1ull << 31) - 1) return RIO_ERR_UNSUPPORTED;
+    return RIO_OK;
+}
+
+extern "C" int rio_device_read_at_plan(rio_ctx* ctx, const uint8_t* d_file, uint64_t len, const uint64_t* d_offsets,
+                                       uint64_t n, rio_read_at_hit* d_hits, uint64_t* d_out_off, void* stream) {
+    if (int rc = read_at_batch_args(ctx, d_file, n, d_offsets, d_hits, d_out_off)) return rc;
+    if (n == 0) return RIO_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    rio_ctx::ReadAtBatch& B = ctx->rab;
+    HIP_TRY(B.tmp.ensure((n + 1) * 8));
+    HIP_TRY(B.cub.ensure(std::max<size_t>(scan_cub_bytes(n), 256)));
+    ReadAtParams P{};
+    P.file = d_file;
+    P.len = len;
+    P.offsets = d_offsets;
+    P.n = n;
+    P.hits = reinterpret_cast<ReadAtResult*>(d_hits);
+    P.tmp = B.tmp.as<uint64_t>();
+    P.out_off = d_out_off;
+    return hip_status(launch_read_at_plan(P, B.cub.p, B.cub.cap, stream_of(ctx, stream)));
+}
+
+extern "C" int rio_device_read_at_copy(rio_ctx* ctx, const uint8_t* d_file, uint64_t len, uint64_t n,
+                                       rio_read_at_hit* d_hits, const uint64_t* d_out_off, uint8_t* d_out,
+                                       uint64_t out_cap, void* stream) {
+    if (int rc = read_at_batch_args(ctx, d_file, n, d_hits, d_out_off, d_out)) return rc;
+    if (n == 0) return RIO_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ctx->fr.sink.ensure(kSinkBytes));
+    ReadAtParams P{};
+    P.file = d_file;
+    P.len = len;
+    P.n = n;
+    P.hits = reinterpret_cast<ReadAtResult*>(d_hits);
+    P.out_off = const_cast<uint64_t*>(d_out_off);
+    P.out = d_out;
+    P.out_cap = out_cap;
+    P.sink = ctx->fr.sink.as<uint8_t>();
+    hipStream_t s = stream_of(ctx, stream);
+    HIP_TRY(launch_read_at_copy(P, s));
+    return hip_status(launch_read_at_snappy(P, s));
 }
 
 // ------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 // rio_device.h — structures shared by the HIP kernels (the .hip files) and the host runtime
 // (rio_ctx.h and the files that include it). Internal to librio; the public boundary is include/rio.h.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "rio.h"
@@ -152,6 +153,31 @@ struct ReadAtResult {
     uint64_t det0, det1;
     uint64_t hdr_len;
     uint64_t payload_off;
+};
+
+// the batched calls hand the same fields out as rio_read_at_hit (rio.h): one layout, read either way
+static_assert(sizeof(rio_read_at_hit) == sizeof(ReadAtResult) && alignof(rio_read_at_hit) == alignof(ReadAtResult) &&
+                  offsetof(rio_read_at_hit, status) == offsetof(ReadAtResult, status) &&
+                  offsetof(rio_read_at_hit, nil) == offsetof(ReadAtResult, nil) &&
+                  offsetof(rio_read_at_hit, len) == offsetof(ReadAtResult, len) &&
+                  offsetof(rio_read_at_hit, detail0) == offsetof(ReadAtResult, det0) &&
+                  offsetof(rio_read_at_hit, detail1) == offsetof(ReadAtResult, det1) &&
+                  offsetof(rio_read_at_hit, hdr_len) == offsetof(ReadAtResult, hdr_len) &&
+                  offsetof(rio_read_at_hit, payload_off) == offsetof(ReadAtResult, payload_off),
+              "rio_read_at_hit is ReadAtResult");
+
+// rio_seek.hip / rio_snappy.hip: a batch of ReadNextAt queries on one file (rio_device_read_at_plan / _copy)
+struct ReadAtParams {
+    const uint8_t* file;      // 16-byte aligned, RIO_DEVICE_PAD readable bytes past len
+    uint64_t len;
+    const uint64_t* offsets;  // [n] (plan)
+    uint64_t n;
+    ReadAtResult* hits;       // [n]
+    uint64_t* tmp;            // [n + 1] scan input (plan)
+    uint64_t* out_off;        // [n + 1] written by the plan, read by the copy
+    uint8_t* out;             // (copy)
+    uint64_t out_cap;
+    uint8_t* sink;            // [kSinkBytes] the context's sink arena (Snappy copy)
 };
 
 // Launch configuration passed from the host runtime.

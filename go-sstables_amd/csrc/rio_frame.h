@@ -85,6 +85,36 @@ __device__ __forceinline__ int read_uvarint(SrcT<B>& s, uint64_t& x) {
     return RIO_ERR_VARINT_OVERFLOW;
 }
 
+// uvarint_buf (rio_dev_util.h: encoding/binary.Uvarint) over bytes [p, p + n) of a byte source
+template <class B>
+__device__ __forceinline__ int uvarint_at(B& get, uint64_t p, uint64_t n, uint64_t& x) {
+    uint64_t v = 0;
+    uint32_t sh = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        if (i == 10) return -(int)(i + 1);
+        const uint32_t b = get(p + i);
+        if (b < 0x80) {
+            if (i == 9 && b > 1) return -(int)(i + 1);
+            x = v | ((uint64_t)b << sh);
+            return (int)(i + 1);
+        }
+        v |= (uint64_t)(b & 0x7F) << sh;
+        sh += 7;
+    }
+    return 0;
+}
+
+// The preamble of the Snappy payload at [pay, pay + plen) by ReadNextAt's rule (read_at_dev, rio_seek.hip): false
+// (ErrCorrupt) for an unusable varint, a length past 32 bits, or one above 22x the element bytes + 64; else its k
+// bytes and the decoded length
+template <class B>
+__device__ __forceinline__ bool snappy_preamble_at(B& get, uint64_t pay, uint64_t plen, uint32_t& k, uint64_t& dl) {
+    dl = 0;
+    const int kk = uvarint_at(get, pay, plen, dl);
+    k = kk > 0 ? (uint32_t)kk : 0u;
+    return kk > 0 && dl <= 0xFFFFFFFFull && dl <= 22ull * (plen - (uint64_t)kk) + 64;
+}
+
 struct Hdr {
     uint64_t u, c, exp_crc, act_crc;
     uint32_t hdr_len, magic_len;

@@ -62,6 +62,11 @@ hipError_t launch_read_at(const uint8_t* f, uint64_t len, uint64_t off, uint8_t*
                           ReadAtResult* res, hipStream_t s);
 hipError_t launch_seek_next(const uint8_t* f, uint64_t len, uint64_t off, uint64_t seek_len, uint8_t* out,
                             uint64_t out_cap, ReadAtResult* res, uint64_t* rec_off, hipStream_t s);
+// the batch of ReadNextAt queries: the hits and offsets; the uncompressed copy (with the capacity rule); rio_snappy.hip:
+// the Snappy copy (after launch_read_at_copy: it reads the rule's marks)
+hipError_t launch_read_at_plan(const ReadAtParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s);
+hipError_t launch_read_at_copy(const ReadAtParams& P, hipStream_t s);
+hipError_t launch_read_at_snappy(const ReadAtParams& P, hipStream_t s);
 int build_seek_map(const uint8_t* f, uint64_t len, const uint64_t* rec_off, const uint8_t* flags, uint64_t n,
                    std::vector<uint64_t>& P, std::vector<uint64_t>& R, hipStream_t s);
 hipError_t launch_index_search(const uint8_t* f, uint64_t len, uint64_t seek_len, const uint8_t* keys,

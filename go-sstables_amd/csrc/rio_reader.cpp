@@ -104,6 +104,8 @@ struct rio_reader {
     bool on_device = false;
     DevBuf dfile;
     std::atomic<uint64_t> seek_len{4096};
+    // MMAP mode: the device arenas of a batch (rio_reader_read_next_at_batch), used under mu and the context's lock
+    DevBuf b_offsets, b_hits, b_out_off, b_out;
     // MMAP mode: the decoded file (built on the first ReadNextAt / SeekNext, then read-only)
     std::atomic<const ReadAtIndex*> ix{nullptr};
     std::unique_ptr<ReadAtIndex> ix_own;
@@ -179,6 +181,10 @@ extern "C" int rio_reader_close(rio_reader* r) {
     r->stream = nullptr;
     r->w_n = 0;
     r->dfile.release();
+    r->b_offsets.release();
+    r->b_hits.release();
+    r->b_out_off.release();
+    r->b_out.release();
     r->on_device = false;
     return RIO_OK;
 }
@@ -524,6 +530,134 @@ extern "C" int rio_reader_read_next_at(rio_reader* r, uint64_t offset, const uin
     const bool expand = r->compression == RIO_COMP_GZIP || r->compression == RIO_COMP_LZW;
     if (rc == RIO_ERR_UNSUPPORTED && expand) return readat_expand(r, offset, res, data, len, is_nil);
     return rc;
+}
+
+// ---- a batch of ReadNextAt calls (rio_reader_read_next_at_batch) ----------------------------------
+// The queries that the reader's device copy of the file answers: one rio_device_read_at_plan / _copy pair under the
+// reader's and the context's lock, the hits, offsets and bytes copied back through the context's staging. The output
+// arena only grows; a batch that needs more than it holds comes back RIO_ERR_CAPACITY with its need in out_off[m]
+// and runs once more.
+static int batch_on_device(rio_reader* r, const std::vector<uint64_t>& offs, std::vector<rio_read_at_hit>& hits,
+                           std::vector<uint64_t>& out_off, std::vector<uint8_t>& out) {
+    const uint64_t m = offs.size();
+    std::lock_guard<std::mutex> g(r->mu);
+    if (!r->open || r->closed) return RIO_ERR_STATE;
+    rio_ctx* ctx = r->ctx;
+    std::lock_guard<std::mutex> cg(ctx->mu);
+    int rc = ensure_on_device(r);
+    if (rc) return rc;
+    HIP_TRY(r->b_offsets.ensure(m * 8));
+    HIP_TRY(r->b_hits.ensure(m * sizeof(rio_read_at_hit)));
+    HIP_TRY(r->b_out_off.ensure((m + 1) * 8));
+    if (r->b_out.cap == 0) HIP_TRY(r->b_out.ensure(1 << 20));
+    if ((rc = h2d_staged(ctx, r->b_offsets.p, reinterpret_cast<const uint8_t*>(offs.data()), m * 8))) return rc;
+    hits.resize(m);
+    out_off.resize(m + 1);
+    for (int attempt = 0; attempt < 2; attempt++) {
+        rc = rio_device_read_at_plan(ctx, r->dfile.as<uint8_t>(), r->size, r->b_offsets.as<uint64_t>(), m,
+                                     r->b_hits.as<rio_read_at_hit>(), r->b_out_off.as<uint64_t>(), nullptr);
+        if (!rc)
+            rc = rio_device_read_at_copy(ctx, r->dfile.as<uint8_t>(), r->size, m, r->b_hits.as<rio_read_at_hit>(),
+                                         r->b_out_off.as<uint64_t>(), r->b_out.as<uint8_t>(), r->b_out.cap, nullptr);
+        if (!rc) rc = d2h_staged(ctx, reinterpret_cast<uint8_t*>(out_off.data()), r->b_out_off.p, (m + 1) * 8);
+        if (rc) return rc;
+        if (out_off[m] <= r->b_out.cap) break;
+        if (attempt) return RIO_ERR_CAPACITY;  // (the same file and offsets: not reached)
+        HIP_TRY(r->b_out.ensure(out_off[m] + 16));
+    }
+    if ((rc = d2h_staged(ctx, reinterpret_cast<uint8_t*>(hits.data()), r->b_hits.p, m * sizeof(rio_read_at_hit)))) return rc;
+    out.resize(out_off[m] + 1);
+    return out_off[m] ? d2h_staged(ctx, out.data(), r->b_out.p, out_off[m]) : RIO_OK;
+}
+
+// the calling thread's last batch: what *data / *out_off point into, and the device path's results before they are
+// merged with the index's and the expanded records
+struct BatchResult {
+    std::vector<uint8_t> data, dev_data, x_data;
+    std::vector<uint64_t> off, dev_offsets, dev_off, x_off;
+    std::vector<rio_read_at_hit> dev_hits;
+    std::vector<uint64_t> dev_query;  // the query each device hit answers
+    std::vector<uint64_t> x_query;    // the queries expanded one by one, in x_off's order
+    std::vector<const uint8_t*> src;  // per query: its record's bytes (null: none)
+};
+static thread_local BatchResult tl_batch;
+
+extern "C" int rio_reader_read_next_at_batch(rio_reader* r, const uint64_t* offsets, uint64_t n, rio_read_at_hit* hits,
+                                             const uint8_t** data, const uint64_t** out_off) {
+    if (!r || !data || !out_off || (n && (!offsets || !hits))) return RIO_ERR_ARG;
+    *data = nullptr;
+    *out_off = nullptr;
+    if (n >= (1ull << 31) - 1) return RIO_ERR_UNSUPPORTED;
+    if (!r->open || r->closed) return RIO_ERR_STATE;
+    BatchResult& B = tl_batch;
+    try {
+        B.off.assign(n + 1, 0);
+        B.src.assign(n, nullptr);
+        B.dev_offsets.clear();
+        B.dev_query.clear();
+        B.x_data.clear();
+        B.x_off.assign(1, 0);
+        B.x_query.clear();
+        // record starts of an index some earlier call built: from it, on this thread. The batch builds none
+        const ReadAtIndex* x = r->ix.load(std::memory_order_acquire);
+        for (uint64_t i = 0; i < n; i++) {
+            const uint64_t j = x && x->n ? x->find(offsets[i]) : 0;
+            if (x && j < x->n) {
+                rio_read_at_hit h{};
+                int nil = 0;
+                h.status = x->record(j, &B.src[i], &h.len, &nil);
+                h.nil = nil;
+                if (h.status != RIO_OK) B.src[i] = nullptr;
+                hits[i] = h;
+            } else {
+                B.dev_offsets.push_back(offsets[i]);
+                B.dev_query.push_back(i);
+            }
+        }
+        const uint64_t m = B.dev_offsets.size();
+        if (m) {
+            if (int rc = batch_on_device(r, B.dev_offsets, B.dev_hits, B.dev_off, B.dev_data)) return rc;
+            const bool expand = r->compression == RIO_COMP_GZIP || r->compression == RIO_COMP_LZW;
+            for (uint64_t k = 0; k < m; k++) {
+                const uint64_t i = B.dev_query[k];
+                rio_read_at_hit h = B.dev_hits[k];
+                if (h.status == RIO_OK && !h.nil) B.src[i] = B.dev_data.data() + B.dev_off[k];
+                if (h.status == RIO_ERR_UNSUPPORTED && expand) {
+                    // located, not expanded: as a file of its own, one record at a time (takes the locks itself)
+                    ReadAtResult res{};
+                    res.len = h.len;
+                    res.payload_off = h.payload_off;
+                    const uint8_t* d = nullptr;
+                    uint64_t l = 0;
+                    int nil = 0;
+                    h.status = readat_expand(r, offsets[i], res, &d, &l, &nil);
+                    h.len = h.status == RIO_OK ? l : 0;
+                    if (h.status == RIO_OK) {
+                        B.x_data.insert(B.x_data.end(), d, d + l);
+                        B.x_off.push_back(B.x_data.size());
+                        B.x_query.push_back(i);
+                    }
+                }
+                hits[i] = h;
+            }
+            // expanded records were appended while x_data grew: their pointers now
+            for (uint64_t t = 0; t < B.x_query.size(); t++) B.src[B.x_query[t]] = B.x_data.data() + B.x_off[t];
+        }
+        for (uint64_t i = 0; i < n; i++)
+            B.off[i + 1] = B.off[i] + (hits[i].status == RIO_OK && !hits[i].nil ? hits[i].len : 0);
+        if (m == n && B.off == B.dev_off) {
+            B.data.swap(B.dev_data);  // every query answered on the device: its arena is the result as it stands
+        } else {
+            B.data.resize(B.off[n] + 1);
+            for (uint64_t i = 0; i < n; i++)
+                if (B.off[i + 1] > B.off[i]) memcpy(B.data.data() + B.off[i], B.src[i], B.off[i + 1] - B.off[i]);
+        }
+    } catch (const std::exception&) {  // an allocation failure is a status, never an exception through the C-ABI
+        return RIO_ERR_CAPACITY;
+    }
+    *data = B.data.data();
+    *out_off = B.off.data();
+    return RIO_OK;
 }
 
 extern "C" int rio_reader_seek_next(rio_reader* r, uint64_t offset, uint64_t* rec_offset, const uint8_t** data,

@@ -1,7 +1,8 @@
 // rio_seek.hip — single records and lookups on a file in HBM: MMapReader.ReadNextAt / SeekNext (k_read_at,
-// k_seek_next), the SeekNext map of a decoded file (k_count91 .. k_seek_jump) that serves the ReadAtI handle, and the
-// DiskKeyIndex searches (k_index_search on the raw file, k_index_search_view on a decoded one). Framing primitives:
-// rio_frame.h. Byte/integer work only; all offsets 64-bit.
+// k_seek_next), a batch of ReadNextAt offsets (k_readat_locate, k_readat_copy), the SeekNext map of a decoded file
+// (k_count91 .. k_seek_jump) that serves the ReadAtI handle, and the DiskKeyIndex searches (k_index_search on the raw
+// file, k_index_search_view on a decoded one). Framing primitives: rio_frame.h. Byte/integer work only; all offsets
+// 64-bit.
 #include <hip/hip_runtime.h>
 
 #include <vector>
@@ -11,6 +12,7 @@
 #include "rio_frame.h"
 #include "rio_launch.h"
 #include "rio_pb.h"
+#include "rio_seg_copy.h"
 #include "rio_wave.h"
 
 namespace rio {
@@ -99,6 +101,107 @@ __global__ void k_read_at(const uint8_t* f, uint64_t len, uint64_t off, uint8_t*
     if (e == RIO_OK) e = read_at_dev(f, len, ver, comp, off, out, out_cap, r, true);
     r.status = e;
     *res = r;
+}
+
+// ------------------------------------------------------------------------------------------
+// A batch of ReadNextAt queries on one file (rio_device_read_at_plan / _copy): what k_read_at answers for one offset,
+// for n of them without a host synchronisation.
+//   k_readat_locate     one lane per query: the file header as k_read_at reads it (a refused one is every hit's
+//                       status), read_at_locate through the lane's 16-byte window, then the codec's part of
+//                       read_at_dev up to the decode: the Snappy preamble and its bounds, gzip / lzw handed back
+//                       located (RIO_ERR_UNSUPPORTED, payload_off / len) or failed on an empty payload. Writes the
+//                       hit and the scan's input: the decoded length of an RIO_OK non-nil record, else 0
+//   k_readat_copy<G>    first (the 16-lane launch only) the capacity rule, one lane per query: an RIO_OK non-nil
+//                       hit whose range ends past out_cap becomes RIO_ERR_CAPACITY. Then, for an uncompressed file,
+//                       copy_ranges (rio_seg_copy.h) from the file's payloads. The host does not know the file's
+//                       compression (no synchronisation), so these and k_readat_snappy (rio_snappy.hip) are all
+//                       launched and each reads the file header for itself
+// The copy kernels trust no field of a hit: a range comes from out_off and is checked against out_cap by
+// copy_ranges, a source from payload_off and is checked against the file.
+// ------------------------------------------------------------------------------------------
+namespace {
+// 256 CUs x 8 blocks of 256 lanes: longer batches go round the grid-stride loop again
+constexpr uint64_t kReadAtGridCap = 2048;
+
+__device__ __forceinline__ int read_at_file_header(const uint8_t* f, uint64_t len, uint32_t& ver, uint32_t& comp) {
+    FrameParams F{};
+    F.file = f;
+    F.len = len;
+    return file_header_status(F, ver, comp);
+}
+}  // namespace
+
+// position n holds the scan's last input, 0
+__global__ void __launch_bounds__(256) k_readat_locate(ReadAtParams P) {
+    // CRC-32C tables (T[0..255] = the byte table), copied here and not by crc32c_tab_init: a second caller changes that
+    // function's out-of-line code, and k_index_search's registers are tuned around it as it is (rio_frame.h)
+    __shared__ uint32_t T[1024];
+    reinterpret_cast<uint4*>(T)[threadIdx.x] = reinterpret_cast<const uint4*>(kCrc32c.t)[threadIdx.x];  // 256 lanes
+    __syncthreads();
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    uint32_t ver, comp;
+    const int he = read_at_file_header(P.file, P.len, ver, comp);
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= P.n; i += stride) {
+        uint64_t need = 0;
+        if (i < P.n) {
+            ReadAtResult r{};
+            int e = he;
+            if (e == RIO_OK) {
+                Hdr h;
+                WinBytes wb{P.file};
+                e = read_at_locate(wb, P.len, ver, comp, P.offsets[i], r, h, T);
+                if (e == RIO_OK && !r.nil) {
+                    if (comp == RIO_COMP_SNAPPY) {
+                        uint32_t k;
+                        uint64_t dl;
+                        const bool ok = snappy_preamble_at(wb, r.payload_off, r.len, k, dl);
+                        r.len = ok ? dl : 0;
+                        if (!ok) e = RIO_ERR_DECOMPRESS;
+                    } else if (comp != RIO_COMP_NONE) {
+                        // read_at_dev's rule: an empty payload fails in the codec, any other is the host's to expand
+                        e = r.len ? RIO_ERR_UNSUPPORTED : (comp == RIO_COMP_GZIP ? RIO_EOF_CODEC : RIO_ERR_DECOMPRESS);
+                    }
+                    if (e == RIO_OK) need = r.len;
+                }
+            }
+            r.status = e;
+            P.hits[i] = r;
+        }
+        P.tmp[i] = need;
+    }
+}
+
+// G lanes per record. kLong = false: records shorter than kLongItem, and the capacity rule; true: the others.
+template <uint32_t G, bool kLong>
+__global__ void __launch_bounds__(256) k_readat_copy(ReadAtParams P) {
+    if (!kLong) {
+        // a hit marked here ends past out_cap, so no copy loop of this launch looks at it (copy_ranges skips the range
+        // before it asks for a source); the launches after this one see the mark
+        const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+        for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P.n; i += stride) {
+            ReadAtResult& h = P.hits[i];
+            if (h.status == RIO_OK && !h.nil && P.out_off[i + 1] > P.out_cap) h.status = RIO_ERR_CAPACITY;
+        }
+    }
+    uint32_t ver, comp;
+    if (read_at_file_header(P.file, P.len, ver, comp) != RIO_OK || comp != RIO_COMP_NONE) return;
+    copy_ranges<G, kLong>(P.n, P.out_off, P.out_cap, P.out, [&](uint64_t j, uint64_t len) __attribute__((always_inline)) -> const uint8_t* {
+        const ReadAtResult& h = P.hits[j];
+        if (h.status != RIO_OK || h.nil || h.len != len || h.payload_off > P.len || len > P.len - h.payload_off)
+            return nullptr;
+        return P.file + h.payload_off;
+    });
+}
+
+hipError_t launch_read_at_plan(const ReadAtParams& P, void* cub_tmp, size_t cub_bytes, hipStream_t s) {
+    hipLaunchKernelGGL(k_readat_locate, dim3(grid_for(P.n + 1, 256, kReadAtGridCap)), dim3(256), 0, s, P);
+    const hipError_t e = launch_offsets_scan(cub_tmp, cub_bytes, P.tmp, P.out_off, P.n, s);
+    return e != hipSuccess ? e : hipGetLastError();
+}
+
+hipError_t launch_read_at_copy(const ReadAtParams& P, hipStream_t s) {
+    launch_short_long(k_readat_copy<16, false>, k_readat_copy<64, true>, P.n, P, s);
+    return hipGetLastError();
 }
 
 // MMapReader.SeekNext (mmap_reader.go:58-128): windowed scan for 91 8d 4c with its skip rule,

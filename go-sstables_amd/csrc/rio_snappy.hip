@@ -29,10 +29,13 @@
 // streams >= 4 GiB; 64-bit addressing, one 64-byte output window per round with lane = byte.
 // Files whose every record is a single literal (k_place sets ScanState::any_mixed otherwise) are
 // copied by k_copy_records (rio_place.hip) and the kernels here exit at once.
+// k_readat_snappy: the wave-per-record decoder on the records of a batch of ReadNextAt queries
+// (rio_device_read_at_copy), any offsets in any order.
 #include <hip/hip_runtime.h>
 
 #include "rio_device.h"
 #include "rio_dev_util.h"
+#include "rio_frame.h"
 #include "rio_launch.h"
 #include "rio_wave.h"
 
@@ -948,6 +951,69 @@ __global__ void __launch_bounds__(64 * kCoopWaves) k_snappy_coop_batch(FrameBatc
                   (uint64_t)gridDim.x * kCoopWaves);
 }
 
+// rio_device_read_at_copy on a Snappy file (the plan: k_readat_locate, rio_seek.hip): the waves stride over the
+// queries, each decoding the record of an RIO_OK non-nil hit into its range of out with coop_record. Here beside
+// coop_file because coop_record is this file's own; P carries what coop_fetch and coop_record read, file and len.
+// A hit keeps the decoded length, not the payload's, so the wave parses the record's header again and takes the
+// stream from it: the 64 bytes from the record's start, one per lane (WaveBytes: header and preamble are at most
+// kReadAtHdrMax + 10 of them), read back lane by lane with every lane parsing the same bytes. Nothing is decoded
+// unless header, preamble, range and hit agree and the payload lies in the file, so a hit that is not the plan's is
+// left alone. A stream that does not decode makes its hit RIO_ERR_DECOMPRESS (coop_record stores inside
+// [out, out + dlen) only). Hits that k_readat_copy marked RIO_ERR_CAPACITY (launched before this kernel) are not
+// RIO_OK any more.
+namespace {
+// the longest record header: v4's checksum reader stops at 36 bytes, v2 / v3 hold three varints and the nil byte
+constexpr uint64_t kReadAtHdrMax = RIO_RECORD_HEADER_V4_MAX;
+static_assert(kReadAtHdrMax >= 31 && kReadAtHdrMax + 10 <= 64 && RIO_DEVICE_PAD >= 64, "header and preamble in one wave's bytes");
+// bytes [base, base + 64) of the file, lane l holding byte l; every lane of the wave asks for the same position
+struct WaveBytes {
+    uint32_t v;
+    uint64_t base;
+    __device__ __forceinline__ uint32_t operator()(uint64_t p) const {
+        return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)(__builtin_amdgcn_readfirstlane((uint32_t)(p - base)) & 63u));
+    }
+};
+}  // namespace
+
+__global__ void __launch_bounds__(64 * kCoopWaves) k_readat_snappy(ReadAtParams Q) {
+    __shared__ CoopLds lds[kCoopWaves];
+    FrameParams P{};
+    P.file = Q.file;
+    P.len = Q.len;
+    uint32_t ver, comp;
+    if (file_header_status(P, ver, comp) != RIO_OK || comp != RIO_COMP_SNAPPY) return;
+    const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint64_t wave = (uint64_t)blockIdx.x * kCoopWaves + wv, nw = (uint64_t)gridDim.x * kCoopWaves;
+    uint8_t* sink = Q.sink + (wave % (kSinkBytes / 64)) * 64;  // placeholder line
+    for (uint64_t i = wave; i < Q.n; i += nw) {
+        const ReadAtResult h = Q.hits[i];
+        const uint64_t d0 = Q.out_off[i], d1 = Q.out_off[i + 1];
+        if (h.status != RIO_OK || h.nil || d1 < d0 || d1 > Q.out_cap || d1 - d0 != h.len) continue;
+        if (h.payload_off > Q.len || h.hdr_len > h.payload_off || h.hdr_len > kReadAtHdrMax) continue;
+        Hdr hd;
+        const uint64_t rs = h.payload_off - h.hdr_len;  // rs <= len: the 64 bytes end inside the file's padding
+        WaveBytes wb{Q.file[rs + lane], rs};
+        if (parse_header_t(wb, rs, h.hdr_len, ~0ull, ver, hd) != RIO_OK) continue;
+        const uint64_t plen = hd.c;
+        if (hd.nil || hd.hdr_len != h.hdr_len || plen > Q.len - h.payload_off) continue;
+        uint32_t k;
+        uint64_t dl;
+        if (!snappy_preamble_at(wb, h.payload_off, plen, k, dl) || dl != h.len) continue;
+        const uint64_t start = h.payload_off + k, slen = plen - k;
+        bool ok;
+        if (slen >> 32) {
+            // a stream past 32-bit positions (never produced by an encoder): one thread, as coop_file takes them
+            ok = lane != 0 || snappy_decode_thread(Q.file + start, slen, Q.out + d0, dl);
+        } else {
+            ok = coop_record(P, lds[wv], lane, start, (uint32_t)slen, (uint32_t)dl, Q.out + d0, sink);
+        }
+        if (!ok && lane == 0) {  // plain stores: the range in out_off stays, its bytes are unspecified
+            Q.hits[i].status = RIO_ERR_DECOMPRESS;
+            Q.hits[i].len = 0;
+        }
+    }
+}
+
 // rio_device_decode_batch: one launch for every lane-decoder file of the batch. The lanes of the grid
 // are split over the files by record count (whole waves per file, so the file's parameters stay
 // wave-uniform scalars), which is what fills the chip when each file alone has fewer records than
@@ -1070,6 +1136,11 @@ __global__ void __launch_bounds__(kSnappyBlock) k_snappy_pipe_batch(FrameBatch B
         }
         w0 += wf;
     }
+}
+
+hipError_t launch_read_at_snappy(const ReadAtParams& P, hipStream_t s) {
+    hipLaunchKernelGGL(k_readat_snappy, dim3(grid_for(P.n, kCoopWaves, kCoopGrid)), dim3(64 * kCoopWaves), 0, s, P);
+    return hipGetLastError();
 }
 
 hipError_t launch_snappy_batch(const FrameBatch& B, hipStream_t s) {

@@ -200,6 +200,20 @@ class IndexHit(ctypes.Structure):
     ]
 
 
+class ReadAtHit(ctypes.Structure):
+    """rio_read_at_hit (include/rio.h): one query of a batched ReadNextAt."""
+
+    _fields_ = [
+        ("status", ctypes.c_int32),
+        ("nil", ctypes.c_int32),
+        ("len", c_uint64),
+        ("detail0", c_uint64),
+        ("detail1", c_uint64),
+        ("hdr_len", c_uint64),
+        ("payload_off", c_uint64),
+    ]
+
+
 RIO_SEEK_END_OTHER = (1 << 63) - 1
 RIO_SEEK_END_EOF = RIO_SEEK_END_OTHER - 1
 
@@ -254,6 +268,9 @@ _SIGS = {
         [c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_uint64, POINTER(c_uint64), POINTER(c_int),
          POINTER(c_uint64), POINTER(c_uint64)],
     ),
+    "rio_device_read_at_plan": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p]),
+    "rio_device_read_at_copy": (
+        c_int, [c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p]),
     "rio_reader_new_file": (c_int, [c_void_p, c_char_p, POINTER(c_void_p)]),
     "rio_reader_new_mmap": (c_int, [c_void_p, c_char_p, POINTER(c_void_p)]),
     "rio_reader_open": (c_int, [c_void_p]),
@@ -265,6 +282,8 @@ _SIGS = {
     "rio_reader_read_next": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_uint64), POINTER(c_int)]),
     "rio_reader_skip_next": (c_int, [c_void_p]),
     "rio_reader_read_next_at": (c_int, [c_void_p, c_uint64, POINTER(c_void_p), POINTER(c_uint64), POINTER(c_int)]),
+    "rio_reader_read_next_at_batch": (
+        c_int, [c_void_p, c_void_p, c_uint64, POINTER(ReadAtHit), POINTER(c_void_p), POINTER(POINTER(c_uint64))]),
     "rio_reader_seek_next": (
         c_int, [c_void_p, c_uint64, POINTER(c_uint64), POINTER(c_void_p), POINTER(c_uint64), POINTER(c_int)]),
     "rio_reader_set_seek_len": (c_int, [c_void_p, c_uint64]),

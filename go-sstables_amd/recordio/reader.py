@@ -180,17 +180,18 @@ class FileReader(_Reader):
 
 
 class MMapReader(_Reader):
-    """recordio.MMapReader (ReadAtI) backed by single-record device kernels."""
+    """recordio.MMapReader (ReadAtI) backed by the reader's decoded index and the single-record device kernels;
+    ReadNextAtBatch takes many offsets through one batched device call."""
 
     _mmap = True
 
     def _not_open(self):
         return GoError(f"reader at '{self.path}' was either not opened yet or is closed already")
 
-    def _err(self, rc, offset):
+    def _err(self, rc, offset, detail=None):
         if rc == L.RIO_ERR_STATE:
             return self._not_open()
-        d0, d1, _ = self._detail()
+        d0, d1 = detail if detail is not None else self._detail()[:2]
         if rc == L.RIO_EOF:
             return EOF  # mmap_reader.go:153-155: bare io.EOF
         v = self.header.fileVersion if self.header else 4
@@ -215,6 +216,29 @@ class MMapReader(_Reader):
         if nil.value:
             return None, None
         return (ctypes.string_at(data.value, n.value) if n.value else b""), None
+
+    def ReadNextAtBatch(self, offsets):  # noqa: N802
+        """[(record | None, err)], element for element what a loop of ReadNextAt(offset) returns, from one
+        rio_reader_read_next_at_batch call: one plan / copy pair on the device for every offset that the
+        reader's decoded index (if an earlier call built one) does not answer."""
+        offsets = [int(o) for o in offsets]
+        n = len(offsets)
+        arr = (c_uint64 * max(n, 1))(*offsets)
+        hits = (L.ReadAtHit * max(n, 1))()
+        data, off = c_void_p(), ctypes.POINTER(c_uint64)()
+        rc = L.lib().rio_reader_read_next_at_batch(self._h, arr, n, hits, byref(data), byref(off))
+        if rc != L.RIO_OK:  # the call's own failure (not opened, a device error): every element's
+            return [(None, self._err(rc, o, (0, 0))) for o in offsets]
+        out = []
+        for i, o in enumerate(offsets):
+            h = hits[i]
+            if h.status != L.RIO_OK:
+                out.append((None, self._err(h.status, o, (h.detail0, h.detail1))))
+            elif h.nil:
+                out.append((None, None))
+            else:
+                out.append((ctypes.string_at(data.value + off[i], off[i + 1] - off[i]) if h.len else b"", None))
+        return out
 
     def SeekNext(self, offset: int):  # noqa: N802
         data, n, nil, ro = c_void_p(), c_uint64(), c_int(), c_uint64()

@@ -963,6 +963,41 @@ int rio_device_read_at(rio_ctx* ctx, const uint8_t* d_file, uint64_t len, uint64
                        uint8_t* d_out, uint64_t out_cap, uint64_t* len_out, int* nil_out,
                        uint64_t* detail0, uint64_t* detail1);
 
+/* ---- batched ReadNextAt on the device: n offsets of one device-resident file in one plan / copy pair, the
+ * shape of rio_sst_stack_value_plan / _copy. Both calls are stream-ordered (a NULL stream is the context's own)
+ * and do no host synchronisation; `d_file` is 16-byte aligned with RIO_DEVICE_PAD readable bytes past `len`.
+ * Any offset value is legal, in any order, with duplicates. Per query the hit is what MMapReader.ReadNextAt
+ * (mmap_reader.go:130-203) gives at that offset:
+ *   status   RIO_OK, or the call's error class (a refused file header gives every hit its status);
+ *   nil      1 for a nil record (RIO_OK, no bytes);
+ *   len      RIO_OK: the decoded length. RIO_ERR_CAPACITY (set by the copy): the decoded length the query needs.
+ *            RIO_ERR_UNSUPPORTED: a gzip / lzw record that is located but not expanded on the device: its payload
+ *            is file bytes [payload_off, payload_off + len). Any other status: 0;
+ *   detail0/1  RIO_ERR_HEADER_CRC: the expected / actual checksum.
+ * rio_device_read_at_plan writes the hits and d_out_off[n + 1], the exclusive sum of the decoded lengths of the
+ * RIO_OK non-nil hits (0 for every other hit); d_out_off[n] is the capacity the copy needs.
+ * rio_device_read_at_copy writes record i to d_out + [d_out_off[i], d_out_off[i + 1]). A RIO_OK non-nil hit whose
+ * range ends past out_cap becomes RIO_ERR_CAPACITY, keeps its len and writes nothing. A Snappy stream that does
+ * not decode makes its hit RIO_ERR_DECOMPRESS with len 0; its range in d_out_off stays and the bytes of that range
+ * are unspecified. Nothing is written outside the ranges. gzip / lzw payloads are not expanded (the hits stay RIO_ERR_UNSUPPORTED).
+ * The plan's scan arenas belong to the context and only grow: a plan that needs larger ones than any before it
+ * frees the old ones, which waits for the device, and two plans of one context must not be in flight on different
+ * streams at once (one context serves one stream at a time for these calls, as for the other plan calls).
+ * Both return RIO_OK for n == 0 without launching anything, RIO_ERR_ARG for a null or misaligned argument,
+ * RIO_ERR_UNSUPPORTED for n >= 2^31 - 1, all before any device call. */
+typedef struct rio_read_at_hit {
+    int32_t status;
+    int32_t nil;
+    uint64_t len;
+    uint64_t detail0, detail1;
+    uint64_t hdr_len;      /* bytes of the record's header */
+    uint64_t payload_off;  /* file offset of the first payload byte */
+} rio_read_at_hit;
+int rio_device_read_at_plan(rio_ctx* ctx, const uint8_t* d_file, uint64_t len, const uint64_t* d_offsets, uint64_t n,
+                            rio_read_at_hit* d_hits, uint64_t* d_out_off, void* stream);
+int rio_device_read_at_copy(rio_ctx* ctx, const uint8_t* d_file, uint64_t len, uint64_t n, rio_read_at_hit* d_hits,
+                            const uint64_t* d_out_off, uint8_t* d_out, uint64_t out_cap, void* stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Reader handles mirroring recordio.ReaderI / recordio.ReadAtI on top of the device path.     */
 /* Returned data pointers: ReadNext until Close (windowed file readers: until the next        */
@@ -994,6 +1029,20 @@ int rio_reader_read_next_at(rio_reader* r, uint64_t offset, const uint8_t** data
                             int* is_nil);
 int rio_reader_seek_next(rio_reader* r, uint64_t offset, uint64_t* rec_offset, const uint8_t** data,
                          uint64_t* len, int* is_nil);
+/* n ReadNextAt calls in one: hits[i] is what rio_reader_read_next_at(offsets[i]) returns (status, nil, len, and
+ * the details of a RIO_ERR_HEADER_CRC in the hit itself), record i is (*data)[(*out_off)[i] .. (*out_off)[i + 1]),
+ * in query order. Thread-safe like the calls above; *data and *out_off (n + 1 entries) are valid until the calling
+ * thread's next batch call or rio_reader_free (a record that does not decode has an empty range here; hdr_len and
+ * payload_off are 0 in hits answered from the index). The batch never builds the reader's decoded index: when an earlier
+ * ReadNextAt / SeekNext has built it, offsets that are record starts are copied from it on the calling thread;
+ * every other offset goes to one rio_device_read_at_plan / _copy pair over the reader's device copy of the file,
+ * whose offsets, hits and bytes come back in three staged copies, each with its own synchronise (the pair runs a
+ * second time when the reader's output arena, which only grows, was too small for the batch). gzip / lzw records that pair locates but does not expand are expanded
+ * one by one, each as a small file of its own: slow, correct, and meant for the odd record, not for bulk reads of
+ * such files. Returns RIO_OK (per-query statuses are in the hits), RIO_ERR_ARG, RIO_ERR_STATE (not open),
+ * RIO_ERR_UNSUPPORTED (n >= 2^31 - 1) or a device failure. */
+int rio_reader_read_next_at_batch(rio_reader* r, const uint64_t* offsets, uint64_t n, rio_read_at_hit* hits,
+                                  const uint8_t** data, const uint64_t** out_off);
 /* MMapReader.seekLen (mmap_reader.go:370, default 4096; tests shrink it to 10) */
 int rio_reader_set_seek_len(rio_reader* r, uint64_t seek_len);
 /* A read-only view of what the ReadAtI calls above answer from (open MMAP-mode readers; RIO_ERR_STATE
