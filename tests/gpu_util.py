@@ -51,6 +51,28 @@ def decode_in_new_context(image) -> dict:
         L.lib().rio_ctx_destroy(h)
 
 
+FRAMING_KNOBS = ("RIO_WALK_LANE", "RIO_CHUNK_BYTES", "RIO_LANE_CHUNK_BYTES")
+
+
+def decoder_with_env(monkeypatch, env: dict) -> DeviceDecoder:
+    """A decoder with a context of its own, created under `env` alone of the framing knobs (the context reads
+    them when it is created)."""
+    for k in FRAMING_KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    return DeviceDecoder(0, own_ctx=True)
+
+
+def decode_with(dec: DeviceDecoder, img) -> dict:
+    """Whole-file decode of `img` by `dec`: info and the arrays, cut to the records delivered."""
+    d_file, n = to_device_file(img)
+    b, info = dec.decode(d_file, n)
+    k = info["n_records"]
+    return dict(info, out=b.out[: info["total_out_bytes"]].cpu().numpy(), out_off=b.out_off[: k + 1].cpu().numpy(),
+                rec_off=b.rec_off[:k].cpu().numpy(), flags=b.flags[:k].cpu().numpy())
+
+
 def assert_exact_or_handed_back_at(g: dict, o: dict, redo, what=""):
     """The result equals the oracle's; or the decode was handed back to the reference reader
     (RIO_ERR_UNSUPPORTED) at a record known to need the redo round, everything before it exact: what

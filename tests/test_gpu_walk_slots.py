@@ -15,6 +15,8 @@ import corpus
 import oracle_py as orc
 from conftest import STATUS
 from gpu_util import assert_same_as_oracle
+from gpu_util import decode_with as _decode
+from gpu_util import decoder_with_env as _decoder
 
 pytestmark = pytest.mark.gpu
 
@@ -26,26 +28,6 @@ FRAMINGS = [pytest.param(e, id=i) for i, e in (("wave64", WAVE64), ("wave4096", 
                                                ("lane4096", LANE4K))]
 # the serial repair writes its slots under either walk: the files made by `embedded` run under both at 4 KiB
 REPAIR_FRAMINGS = [pytest.param(e, id=i) for i, e in (("wave4096", WAVE4K), ("lane4096", LANE4K))]
-
-
-def _decoder(monkeypatch, env):
-    from recordio.device import DeviceDecoder
-
-    for k in ("RIO_WALK_LANE", "RIO_CHUNK_BYTES", "RIO_LANE_CHUNK_BYTES"):
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    return DeviceDecoder(0, own_ctx=True)  # the context reads the framing knobs when it is created
-
-
-def _decode(dec, img) -> dict:
-    from recordio.device import to_device_file
-
-    d_file, n = to_device_file(img)
-    b, info = dec.decode(d_file, n)
-    k = info["n_records"]
-    return dict(info, out=b.out[: info["total_out_bytes"]].cpu().numpy(), out_off=b.out_off[: k + 1].cpu().numpy(),
-                rec_off=b.rec_off[:k].cpu().numpy(), flags=b.flags[:k].cpu().numpy())
 
 
 _oracle = {}
